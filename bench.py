@@ -7,7 +7,7 @@ derivative -> obs -> reward -> done (+ auto-reset / done compaction), reading th
 actions from and writing obs / reward / done into a 16-slot on-device rollout ring
 (PPO-style rollout buffer, > 256 MiB Infinity Cache, so the I/O streams from HBM).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \\
          --master-port P bench.py --gpus N ...
 
@@ -16,10 +16,15 @@ collective on the step path (barrier + max-over-ranks timing only).  `--gpus N` 
 a torch.distributed.run environment (no WORLD_SIZE) spawns the N rank processes itself
 (child processes started before anything touches the GPU; rank r pins cuda:r).  Default
 scaling is "strong": BASELINE's 1,048,576 envs in total, split over the N GPUs
-(configs[2]: 131,072 per GPU at N = 8; N = 1 is the 1M-env config itself); for N > 1
-the line also carries the weak 1M-per-GPU run and the step + RCCL gather of obs /
-reward / done to rank 0 (north_star's optional learner gather) in `extra_lines`.
+(configs[2]: 131,072 per GPU at N = 8; N = 1 is the 1M-env config itself).
 --scaling weak makes the weak run the headline.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the
+line.  --full adds what else the headline run measures: the CPU baseline, fp32 drift,
+the cold-state probe and `extra_lines` (fp64 and RK4 lines; for N > 1 the weak
+1M-per-GPU run and the step + RCCL gather of obs / reward / done to rank 0, north_star's
+optional learner gather); --no-cpu-baseline / --no-drift / --no-extras take parts of
+--full away.
 """
 import argparse
 import math
@@ -58,10 +63,21 @@ def parse(argv=None):
                    help="step mode: launch each timed window's first H (even) steps as a graph of "
                         "their own, so the GPU starts on them while the host submits the rest "
                         "(0 = off)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-drift", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline figure, everything else the headline run measures "
+                        "or checks: the CPU baseline, fp32 drift vs the fp64 kernel, the cold-state "
+                        "probe and the extra lines (fp64 / RK4; N > 1: the other scaling mode and "
+                        "the gather to rank 0).  Off: set up, warm up, time the steps, print the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="step / rollout mode: after the timed steps write the obs, reward and done "
+                        "of the last step of the first window after warm-up (rank 0's shard) as "
+                        "DIR/<name>.npy, finite numbers only: inf / NaN entries as 0 and coded "
+                        "in nonfinite.npy (see dump_outputs)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    p.add_argument("--no-drift", action="store_true", help="--full without the fp32 drift check")
     p.add_argument("--no-extras", action="store_true",
-                   help="skip the extra lines of the headline run (fp64 reference precision)")
+                   help="--full without the extra lines of the headline run (fp64 reference "
+                        "precision, RK4, cold-state probe; N > 1: scaling and gather lines)")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
     p.add_argument("--system", choices=["lorenz3", "lorenz4", "pmsm", "hr"], default="lorenz3",
                    help="lorenz3 = the BASELINE headline (dynamic.py env); pmsm = cfg4")
@@ -915,7 +931,7 @@ class _Lane:
 
 
 def measure_steps(args, torch, dist, nat, env, device, world, rank, rollout, min_window_s=0.2,
-                  subs=None):
+                  subs=None, keep_outputs=False):
     """Time EXACTLY K env steps (K = --steps; rollout mode: --steps rounded down to whole
     --K launches), each timed window bracketed by a barrier + torch.cuda.synchronize()
     on both sides.  When one window is shorter than `min_window_s` (e.g. the driver's
@@ -971,17 +987,37 @@ def measure_steps(args, torch, dist, nat, env, device, world, rank, rollout, min
                 with torch.cuda.graph(ln.graph, stream=ln.stream):
                     for _ in range(L):
                         ln.one()
+                ln.slot_graph = (ln.counter - 1) % R  # the ring slot a replay writes last
                 if rem_n:
                     ln.graph_rem = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(ln.graph_rem, stream=ln.stream):
                         for _ in range(rem_n):
                             ln.one()
+                    ln.slot_rem = (ln.counter - 1) % R
                 if H and not E:
                     ln.graph_head = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(ln.graph_head, stream=ln.stream):
                         for _ in range(H):
                             ln.one()
+                    ln.slot_head = (ln.counter - 1) % R
     torch.cuda.synchronize(device)
+
+    def last_slot(ln, nlaunch):  # the ring slot that run(nlaunch) wrote last (mirrors run)
+        slot = eager = (ln.counter - 1) % R
+        if not use_graph:
+            return eager
+        if E and nlaunch >= E:
+            nlaunch -= E
+        elif H and nlaunch >= H:
+            slot = ln.slot_head
+            nlaunch -= H
+        if nlaunch // L:
+            slot = ln.slot_graph
+        r = nlaunch % L
+        if rem_n and r >= rem_n:
+            slot = ln.slot_rem
+            r -= rem_n
+        return eager if r else slot
 
     def run(nlaunch):  # exactly nlaunch launches on every lane, the lanes interleaved
         if not use_graph:
@@ -1027,7 +1063,9 @@ def measure_steps(args, torch, dist, nat, env, device, world, rank, rollout, min
         fix_parity(max(warm, L))
     torch.cuda.synchronize(device)
 
-    def window():
+    kept = []
+
+    def window(keep=False):
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize(device)
@@ -1045,13 +1083,20 @@ def measure_steps(args, torch, dist, nat, env, device, world, rank, rollout, min
         t1 = time.perf_counter()
         if world > 1:
             dist.barrier()
+        if keep:  # device copies of the last step's obs / reward / done, one tuple per lane
+            for ln in lanes:
+                s = last_slot(ln, launches)
+                kept.append(tuple(b[s, -1].clone() for b in ln.buf[1:]))
+            torch.cuda.synchronize(device)
         fix_parity(launches)
         base = ev[0][0]
         span = (max(base.elapsed_time(e1) for _, e1 in ev)
                 - min(0.0, min(base.elapsed_time(e0) for e0, _ in ev)))
         return t1 - t0, span
 
-    first = window()
+    # the step count up to the end of this first window is fixed by the arguments (the count
+    # of windows after it depends on the clock), so --dump-outputs takes its arrays here
+    first = window(keep=keep_outputs)
     # windows until min_window_s are timed in total: batches sized from the windows
     # so far (the first window after warm-up runs slower than the rest), every rank
     # running the same count (MAX over ranks)
@@ -1082,7 +1127,7 @@ def measure_steps(args, torch, dist, nat, env, device, world, rank, rollout, min
         "steps": K, "T": T, "ring": R, "graph_len": L, "graph": use_graph,
         "graph_rem": rem_n, "graph_head": 0 if E else H, "head_eager": E, "streams": len(lanes),
         "warmup": warm, "launches": launches * need, "windows": need,
-        "elapsed": elapsed, "ev_ms": ev_ms,
+        "elapsed": elapsed, "ev_ms": ev_ms, "outputs": kept,
         "timing": {
             "requested_steps": args.steps, "steps_per_window": K, "windows": need,
             "timed_steps_total": K * need, "timed_seconds": elapsed,
@@ -1094,6 +1139,54 @@ def measure_steps(args, torch, dist, nat, env, device, world, rank, rollout, min
                       "window time (MAX over ranks)" % (min_window_s * 1e3),
         },
     }
+
+
+DUMP_MAX_BYTES = 60 * 1000 * 1000  # of the .npy files together (the limit is 64 MB)
+
+
+def nonfinite_code(vals):
+    """[N, C] floats -> [N] codes: base-4 digit j says what column j holds (0 a finite
+    number, 1 +inf, 2 -inf, 3 NaN); 0 = the whole row is finite.  C <= 12, so that every
+    code is exact in float32."""
+    import numpy as np
+
+    assert vals.shape[1] <= 12
+    cls = np.where(np.isnan(vals), 3, np.where(vals == np.inf, 1, np.where(vals == -np.inf, 2, 0)))
+    return (cls * 4 ** np.arange(vals.shape[1])).sum(1)
+
+
+def dump_outputs(path, outputs, f64=False):
+    """--dump-outputs DIR: what a caller of the timed path receives from one step -- obs
+    [N, obs_dim], reward [N], done [N] of this rank's shard (the lanes of --streams S in
+    global-id order) -- as DIR/obs.npy, reward.npy, done.npy in the env's float type (done
+    as 0 / 1 / 2 in it).  `outputs` are measure_steps's device copies from the last step of
+    the first window after warm-up: warm-up and that window run a step count the arguments
+    fix, and states, actions and noise are seeded, so the same arguments give the same
+    arrays on every run and build.
+
+    Every file holds finite numbers only.  About 1 % of LORENZ3's U(-30, 30)^3 initial
+    states overflow under Euler dt = 0.01 (see fp32_drift), and such an env's obs and
+    reward are inf / NaN from then on: those entries are written as 0, and
+    DIR/nonfinite.npy [N] says per env which they were and what they held
+    (nonfinite_code over the row obs | reward), so nothing of the outputs is lost.
+
+    Above DUMP_MAX_BYTES in all, the same seeded sample of env rows (ascending ids) of
+    each array is written."""
+    import numpy as np
+
+    dt = np.float64 if f64 else np.float32
+    obs, rew, done = (np.concatenate([o[j].cpu().numpy() for o in outputs]).astype(dt)
+                      for j in range(3))
+    n = obs.shape[0]
+    rows = DUMP_MAX_BYTES // ((obs.shape[1] + 3) * obs.itemsize)
+    if n > rows:
+        idx = np.sort(np.random.default_rng(0).choice(n, rows, replace=False))
+        obs, rew, done = obs[idx], rew[idx], done[idx]
+    code = nonfinite_code(np.concatenate([obs, rew[:, None]], 1)).astype(dt)
+    obs, rew = (np.where(np.isfinite(a), a, 0).astype(dt) for a in (obs, rew))
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("obs", obs), ("reward", rew), ("done", done), ("nonfinite", code)):
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def free_port():
@@ -1190,9 +1283,11 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
+    if args.dump_outputs and args.mode not in ("step", "rollout"):
+        raise SystemExit("bench.py: --dump-outputs is for --mode step and --mode rollout")
     headline = args.system == "lorenz3" and args.mode == "step"
     cpu = None
-    if rank == 0 and world == 1 and headline and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and headline and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds)  # first: its worker processes start before
         #                                       anything initialises the GPU
     # LZ_BENCH_BACKEND=gloo + ranks sharing a GPU: rehearsal of the multi-rank path on a
@@ -1240,7 +1335,10 @@ def main():
         return
     rollout = args.mode == "rollout"
     subs = make_subs(args, gl, n, start, local, kw) if not rollout else None
-    tm = measure_steps(args, torch, dist, nat, env, device, world, rank, rollout, subs=subs)
+    tm = measure_steps(args, torch, dist, nat, env, device, world, rank, rollout, subs=subs,
+                       keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tm["outputs"], f64=args.dtype == "float64")
     sub_n = subs[0].num_envs if subs else n
     for e in subs or []:
         e.close()
@@ -1318,6 +1416,8 @@ def main():
         out["roofline"]["flop_per_env_step"] = RK4_FLOP[args.system]
     headline = args.system == "lorenz3" and not rollout and "integrator" not in kw
     env.close()
+    # everything below measures or checks something other than the line's own figure: --full
+    headline = headline and args.full
     if rank == 0 and world == 1 and headline and args.dtype == "float32" and not args.no_extras:
         cs = cold_state_probe(gl, nat, torch, device, n)
         cs["frac_cold_scaled"] = out["roofline"]["frac"] * cs["us_per_launch_warm"] / cs["us_per_launch_cold"]

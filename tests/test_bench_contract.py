@@ -140,6 +140,103 @@ def test_bench_line_contract_steps20():
     assert "hipGraph replay of 20 lz_step launches" in d["config"]["launch"]
 
 
+def test_plain_run_options_and_dump_files(tmp_path, monkeypatch):
+    """--full is off by default and the --no-* options only take parts of it away;
+    dump_outputs writes obs / reward / done of all lanes in id order in the env's float
+    type, finite numbers only (inf / NaN entries as 0, what they held coded per env in
+    nonfinite.npy), and above the byte budget the same seeded rows of each array."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--no-drift", "--dump-outputs", "d"])
+    assert a.full and a.no_drift and not a.no_extras and a.dump_outputs == "d"
+    g = torch.Generator().manual_seed(0)
+    lanes = [(torch.rand((n, 6), generator=g), torch.rand((n,), generator=g),
+              torch.randint(0, 3, (n,), generator=g, dtype=torch.uint8)) for n in (5, 7)]
+    bench.dump_outputs(str(tmp_path / "a"), lanes)
+    obs, rew, done = (np.load(tmp_path / "a" / (k + ".npy")) for k in ("obs", "reward", "done"))
+    assert obs.dtype == rew.dtype == done.dtype == np.float32
+    assert np.array_equal(obs, torch.cat([ln[0] for ln in lanes]).numpy())
+    assert np.array_equal(rew, torch.cat([ln[1] for ln in lanes]).numpy())
+    assert np.array_equal(done, torch.cat([ln[2] for ln in lanes]).numpy().astype(np.float32))
+    bench.dump_outputs(str(tmp_path / "b"), [tuple(t.double() for t in ln) for ln in lanes], f64=True)
+    assert np.load(tmp_path / "b" / "obs.npy").dtype == np.float64
+    assert not np.load(tmp_path / "a" / "nonfinite.npy").any()
+    # env 1: obs[2] = +inf, obs[5] = NaN, reward = -inf; env 6: obs[0] = -inf
+    bad = [tuple(t.clone() for t in ln) for ln in lanes]
+    bad[0][0][1, 2], bad[0][0][1, 5], bad[0][1][1] = float("inf"), float("nan"), float("-inf")
+    bad[1][0][1, 0] = float("-inf")
+    bench.dump_outputs(str(tmp_path / "e"), bad)
+    eo, er, ed, ec = (np.load(tmp_path / "e" / (k + ".npy")) for k in ("obs", "reward", "done", "nonfinite"))
+    assert ec.dtype == np.float32 and ec.shape == (12,)
+    assert ec[1] == 1 * 4 ** 2 + 3 * 4 ** 5 + 2 * 4 ** 6 and ec[6] == 2 and np.count_nonzero(ec) == 2
+    assert all(np.isfinite(x).all() for x in (eo, er, ed, ec))
+    assert eo[1, 2] == eo[1, 5] == er[1] == eo[6, 0] == 0 and np.array_equal(ed, done)
+    eo[1, [2, 5]], eo[6, 0], er[1] = obs[1, [2, 5]], obs[6, 0], rew[1]
+    assert np.array_equal(eo, obs) and np.array_equal(er, rew)  # every other entry untouched
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * (6 + 3) * 4)  # room for 4 rows
+    for d in ("c", "d"):
+        bench.dump_outputs(str(tmp_path / d), lanes)
+    small = [np.load(tmp_path / "c" / (k + ".npy")) for k in ("obs", "reward", "done")]
+    assert [s.shape for s in small] == [(4, 6), (4,), (4,)]
+    rows = [int(np.flatnonzero((obs == r).all(1))[0]) for r in small[0]]
+    assert rows == sorted(set(rows)) and np.array_equal(small[1], rew[rows])
+    assert all(np.array_equal(s, np.load(tmp_path / "d" / (k + ".npy")))
+               for s, k in zip(small, ("obs", "reward", "done")))
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run carries none of --full's measurements, and --dump-outputs writes the
+    last step of the first window after warm-up: bit for bit what an independent handle
+    gives when it is stepped eagerly through the same slots of the same seeded action ring
+    (--steps 20 --warmup 5: 5 eager steps, a 64-step graph replay, the 20-step remainder
+    graph; the captures advance the ring's slot counter without stepping).  The files
+    hold finite numbers only: an overflowed env's inf / NaN entries are 0 in obs / reward
+    and coded in nonfinite.npy."""
+    import numpy as np
+    import torch
+
+    import gym_lorenz as gl
+
+    n = 4099
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20",
+                        "--warmup", "5", "--envs", str(n), "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 20 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    assert not {"cpu_baseline", "fp32_drift", "extra_lines"} & set(d)
+    assert "cold_state" not in d["roofline"] and "traffic" in d["roofline"]
+    dev = torch.device("cuda", 0)
+    acts = torch.rand((16, 1, n, 3), generator=torch.Generator(device=dev).manual_seed(1000),
+                      device=dev) * 2 - 1
+    be = gl.BatchedEnv("lorenz3", n, dtype="float32", seed=0, autoreset=True, device=0)
+    be.reset()
+    for k in list(range(5)) + list(range(5, 69)) + list(range(69, 89)):
+        o, rw, dn = be.step(acts[k % 16, 0])
+    o, rw, dn = o.cpu().numpy(), rw.cpu().numpy(), dn.cpu().numpy().astype(np.float32)
+    be.close()
+    row = np.concatenate([o, rw[:, None]], 1)
+    cls = np.select([np.isnan(row), row == np.inf, row == -np.inf], [3, 1, 2], 0)
+    code = (cls * 4 ** np.arange(7)).sum(1).astype(np.float32)
+    fin = np.isfinite(row)
+    want = {"obs": np.where(fin[:, :6], o, 0), "reward": np.where(fin[:, 6], rw, 0), "done": dn,
+            "nonfinite": code}
+    for name, w in want.items():
+        got = np.load(tmp_path / (name + ".npy"))
+        assert got.dtype == np.float32 and got.shape == w.shape
+        assert np.isfinite(got).all(), name
+        assert np.array_equal(got, w), name
+
+
 @pytest.mark.parametrize("mode,extra", [("rollout", ["--K", "2048"]),
                                         ("policy", ["--policy", "attn", "--K", "2048"]),
                                         ("step", [])])

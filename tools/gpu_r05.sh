@@ -16,7 +16,7 @@ case $STAGE in
 new)
   timeout -k 10 900 $PYT -m gpu --maxfail=8 tests/test_gpu_default_launch.py tests/test_gpu_step_multi.py \
     tests/test_gpu_resident.py tests/test_gpu_policy_branches.py > $O/new_tests.txt 2>&1 || exit 1
-  LZ_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 > $O/bench_gpus2_gloo.json 2> $O/bench_gpus2_gloo.err
+  LZ_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 > $O/bench_gpus2_gloo.json 2> $O/bench_gpus2_gloo.err
   ;;
 ic)  # the headline state's reuse distance: bench.py as is (warm) vs a 2 x 192 MiB copy after every step (cold)
   for r in 1 2; do for m in 0 192; do
@@ -163,10 +163,10 @@ ab8)  # attention i8x4 layer 1 software-pipelined (tile t + 1's MFMAs before til
 final)  # the closing run on the final tree: every GPU test, smoke, the bench lines and the headline's rocprof summary
   timeout -k 10 1000 $PYT -x -m gpu tests > $O/gpu_tests.txt 2>&1 || exit 1
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')" > $O/smoke.txt 2>&1 || exit 1
-  timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
-  timeout -k 10 200 python bench.py --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err || exit 1
+  timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
+  timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err || exit 1
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv \
-    -- python bench.py --no-cpu-baseline --no-drift > $O/bench_prof.json 2> $O/bench_prof.err || exit 1
+    -- python bench.py --full --no-cpu-baseline --no-drift > $O/bench_prof.json 2> $O/bench_prof.err || exit 1
   ;;
 ab9)  # attention i8x4 row shifts as per-value ds_read_i16 (no VALU unpack) vs r05d
   timeout -k 10 900 $PYT -m gpu --maxfail=5 tests/test_gpu_policy_i8x4.py > $O/tests.txt 2>&1 || exit 1
@@ -182,9 +182,9 @@ pmc_mlp)  # counters of the MlpPolicy rollout, float32 vs i8x4 (PMSM 32,768 x 20
 dist)  # the driver's N > 1 launch path on this 1-GPU box: torchrun + RCCL at world size 1, and the
        # refusal of more nccl ranks than GPUs (must exit non-zero, not share the card)
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-    --master-port 29517 bench.py --gpus 1 --steps 400 --warmup 40 > $O/torchrun_n1.json 2> $O/torchrun_n1.err || exit 1
+    --master-port 29517 bench.py --full --gpus 1 --steps 400 --warmup 40 > $O/torchrun_n1.json 2> $O/torchrun_n1.err || exit 1
   if timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29518 bench.py --gpus 2 --steps 400 --warmup 40 > $O/torchrun_n2.json 2> $O/torchrun_n2.err; then
+    --master-port 29518 bench.py --full --gpus 2 --steps 400 --warmup 40 > $O/torchrun_n2.json 2> $O/torchrun_n2.err; then
     echo "UNEXPECTED: 2 nccl ranks on 1 GPU ran" > $O/refusal.txt; exit 1
   else
     echo "refused as intended (exit $?)" > $O/refusal.txt
@@ -237,12 +237,12 @@ full)
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')" > $O/smoke.txt 2>&1
   ;;
 bench)
-  timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
-  timeout -k 10 200 python bench.py --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err || exit 1
+  timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
+  timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err || exit 1
   ;;
 bench_all)
-  timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
-  timeout -k 10 200 python bench.py --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err || exit 1
-  LZ_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 > $O/bench_gpus2_gloo.json 2> $O/bench_gpus2_gloo.err
+  timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
+  timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err || exit 1
+  LZ_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 > $O/bench_gpus2_gloo.json 2> $O/bench_gpus2_gloo.err
   ;;
 esac

@@ -18,8 +18,8 @@ run rollout_pmsm_gpus2_gloo 300 python bench.py --gpus 2 --system pmsm --mode ro
 run policy_attn_hr_gpus2_gloo 300 python bench.py --gpus 2 --system hr --mode policy --policy attn --envs 65536 --K 2048 --steps 4096
 run policy_mlp_pmsm_gpus2_gloo 300 python bench.py --gpus 2 --system pmsm --mode policy --policy mlp --envs 65536 --K 2048 --steps 4096 --vecnorm-update rollout
 unset LZ_BENCH_BACKEND
-run bench_default 300 python bench.py
-run bench_steps20 300 python bench.py --steps 20 --warmup 5
+run bench_default 300 python bench.py --full
+run bench_steps20 300 python bench.py --full --steps 20 --warmup 5
 for n in 24576 24608 28672; do
   for v in 0 268435456; do
     run pmsm_${n}_v$v 120 python bench.py --system pmsm --mode rollout --envs $n --K 2048 --steps 8192 --variant $v --no-cpu-baseline --no-drift --no-extras

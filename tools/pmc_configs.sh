@@ -7,7 +7,7 @@ O=gpurun_out/pmc_cfg
 mkdir -p $O
 pass() {  # pass <name> <counter> bench args...
   local name=$1 c=$2; shift 2
-  timeout -k 10 180 rocprofv3 --pmc $c -d $O/$name.$c -o run --output-format csv -- python bench.py "$@" --no-cpu-baseline --no-drift > $O/$name.$c.log 2>&1
+  timeout -k 10 180 rocprofv3 --pmc $c -d $O/$name.$c -o run --output-format csv -- python bench.py --full "$@" --no-cpu-baseline --no-drift > $O/$name.$c.log 2>&1
 }
 one() {  # one <name> <mangled> <match> <envs> <alg_bytes> bench args...
   local name=$1 mangled=$2 match=$3 envs=$4 alg=$5; shift 5

@@ -6,7 +6,7 @@ set -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out/pmc_head
 mkdir -p $O
-timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python bench.py --no-cpu-baseline --no-extras > $O/trace.log 2>&1 || exit 1
+timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python bench.py --full --no-cpu-baseline --no-extras > $O/trace.log 2>&1 || exit 1
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 180 rocprofv3 --pmc $c -d $O/$c -o run --output-format csv -- python bench.py --launch eager --steps 400 --warmup 40 --no-cpu-baseline --no-drift --no-extras > $O/$c.log 2>&1 || exit 1
 done

@@ -17,7 +17,7 @@ one() {  # one <name> <mangled> <match> <envs> <alg_bytes> bench args...
   pass $name WRITE_SIZE "$@" || return 1
   python tools/pmc_generic.py $O/$name.FETCH_SIZE $O/$name.WRITE_SIZE "$mangled" "$match" $envs $alg $O/${name}_pmc_summary.json | tee -a $O/summary.jsonl
 }
-timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/head.trace -o run --output-format csv -- python bench.py --no-cpu-baseline --no-extras > $O/head.trace.log 2>&1 || exit 1
+timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/head.trace -o run --output-format csv -- python bench.py --full --no-cpu-baseline --no-extras > $O/head.trace.log 2>&1 || exit 1
 one lz_step_1M _ZN2lz6k_stepINS_5SysL3IfEEfLi0EEEvNS_5KArgsE "k_step<lz::SysL3<float>, float, 0>" 1048576 68157440 \
     --launch eager --steps 400 --warmup 40 || exit 1
 one cfg2_l3_65k _ZN2lz6k_stepINS_5SysL3IfEEfLi0EEEvNS_5KArgsE "k_step<lz::SysL3<float>, float, 0>" 65536 4259840 \

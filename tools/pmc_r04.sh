@@ -24,7 +24,7 @@ one() {  # one <name> <mangled> <match> <envs> <alg_bytes> bench args...
   python tools/pmc_generic.py $O/$name.FETCH_SIZE $O/$name.WRITE_SIZE "$mangled" "$match" $envs $alg \
     $O/${name}_pmc_summary.json | tee -a $O/summary.jsonl
 }
-want head && { timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/head.trace -o run --output-format csv -- python bench.py \
+want head && { timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/head.trace -o run --output-format csv -- python bench.py --full \
   --no-cpu-baseline --no-extras > $O/head.trace.log 2>&1 || exit 1; }
 E="--launch eager"
 one lz_step_1M _ZN2lz12k_step_multiINS_5SysL3IfEEfLi4ELb0EEEvNS_5KArgsE "k_step_multi<lz::SysL3<float>, float, 4" \
