@@ -40,35 +40,10 @@ lz_status fail(lz_status s, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(LZ_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-struct SysDesc {
-  int state_dim, action_dim, obs_dim, init_dim, n_planes;
-  int step_plane;
-};
-
-SysDesc describe(int system) {
-  switch (system) {
-    case LZ_SYS_LORENZ3: return {3, 3, 6, 3, 4, LZ_L3_STEP};
-    case LZ_SYS_LORENZ4: return {8, 3, 8, 8, 9, LZ_L4_STEP};
-    case LZ_SYS_PMSM: return {6, 2, 6, 6, 11, LZ_PMSM_STEP};
-    case LZ_SYS_T1: return {3, 2, 6, 3, 4, LZ_T1_STEP};
-    case LZ_SYS_T2: return {8, 3, 8, 8, 9, LZ_T2_STEP};
-    case LZ_SYS_TP: return {6, 2, 6, 6, 7, LZ_TP_STEP};
-    case LZ_SYS_SC: return {3, 2, 6, 3, 4, LZ_SC_STEP};
-    default: return {6, 2, 6, 7, 10, LZ_HR_STEP};
-  }
-}
-
-// element size of plane p (T planes, f32 planes, i32 planes)
-int plane_elem(int system, int f64, int p) {
-  const SysDesc d = describe(system);
+// element size of plane p (T planes, then the f32 / i32 planes; PMSM handles are float32)
+int plane_elem(const lz::SysInfo& d, int f64, int p) {
   if (p < 0 || p >= d.n_planes) return 0;
-  if (p == d.step_plane) return 4;
-  const int t = f64 ? 8 : 4;
-  switch (system) {
-    case LZ_SYS_PMSM: return 4;                   // float32 / int32 throughout
-    case LZ_SYS_HR: return p <= LZ_HR_SIGMA ? t : 4;  // filtered_action is float32
-    default: return t;
-  }
+  return p < d.t_planes && f64 ? 8 : 4;
 }
 
 }  // namespace
@@ -82,7 +57,7 @@ lz_status set_error(lz_status s, const char* msg) {
 
 struct lz_handle {
   lz_config cfg;
-  SysDesc desc;
+  const lz::SysInfo* desc;  // the system's host-side facts (lz_internal.h)
   int f64;
   hipStream_t stream;
   void* planes[lz::kMaxPlanes];
@@ -208,7 +183,7 @@ lz_status lz_create(const lz_config* cfg_in, lz_handle** out) {
     return fail(LZ_ERR_INVALID, "unknown system %d", cfg.system);
   if (cfg.dtype != LZ_DTYPE_F32 && cfg.dtype != LZ_DTYPE_F64)
     return fail(LZ_ERR_INVALID, "unknown dtype %d", cfg.dtype);
-  if (cfg.system == LZ_SYS_PMSM && cfg.dtype != LZ_DTYPE_F32)
+  if (!lz::sys_info(cfg.system).has_f64 && cfg.dtype != LZ_DTYPE_F32)
     return fail(LZ_ERR_UNSUPPORTED, "PMSM is float32 only (the reference computes it in float32)");
   if (cfg.num_envs <= 0 || cfg.num_envs > (int64_t)INT32_MAX)
     return fail(LZ_ERR_INVALID, "num_envs must be in [1, 2^31-1], got %lld", (long long)cfg.num_envs);
@@ -231,7 +206,7 @@ lz_status lz_create(const lz_config* cfg_in, lz_handle** out) {
   std::memset(h->planes, 0, sizeof h->planes);
   h->counters = nullptr;
   h->bc = nullptr;
-  h->desc = describe(cfg.system);
+  h->desc = &lz::sys_info(cfg.system);
   h->f64 = cfg.dtype == LZ_DTYPE_F64;
   h->stream = nullptr;
   h->ticks = nullptr;
@@ -269,8 +244,8 @@ lz_status lz_create(const lz_config* cfg_in, lz_handle** out) {
   h->cfg = cfg;
 
   const int64_t n = cfg.num_envs;
-  for (int p = 0; p < h->desc.n_planes; ++p) {
-    const int es = plane_elem(cfg.system, h->f64, p);
+  for (int p = 0; p < h->desc->n_planes; ++p) {
+    const int es = plane_elem(*h->desc, h->f64, p);
     if (hipMalloc(&h->planes[p], (size_t)n * es) != hipSuccess) {
       lz_destroy(h);
       return fail(LZ_ERR_OOM, "hipMalloc of state plane %d (%lld x %d B) failed", p, (long long)n, es);
@@ -348,12 +323,11 @@ lz_status lz_io_sizes_for(const lz_config* cfg, int32_t K, int64_t cap, lz_io_si
   if (!cfg || !out) return fail(LZ_ERR_INVALID, "config/out is NULL");
   if (cfg->system < LZ_SYS_LORENZ3 || cfg->system > LZ_SYS_SC) return fail(LZ_ERR_INVALID, "unknown system");
   if (cfg->num_envs < 1 || K < 0 || cap < 0) return fail(LZ_ERR_INVALID, "num_envs >= 1, K >= 0, cap >= 0");
-  const SysDesc d = describe(cfg->system);
+  const lz::SysInfo& d = lz::sys_info(cfg->system);
   const int64_t n = cfg->num_envs, steps = K > 0 ? K : 1;
-  const int64_t t = (cfg->dtype == LZ_DTYPE_F64 && cfg->system != LZ_SYS_PMSM) ? 8 : 4;
-  const bool needs_act = cfg->system != LZ_SYS_LORENZ4 && cfg->system != LZ_SYS_SC;
+  const int64_t t = (cfg->dtype == LZ_DTYPE_F64 && d.has_f64) ? 8 : 4;
   std::memset(out, 0, sizeof *out);
-  out->actions = needs_act ? steps * n * d.action_dim * 4 : 0;
+  out->actions = d.uses_action ? steps * n * d.action_dim * 4 : 0;
   out->noise = K > 0 ? 0 : n * 3 * 8;
   out->obs = steps * n * d.obs_dim * t;
   out->rew = steps * n * t;
@@ -367,7 +341,7 @@ lz_status lz_io_sizes_for(const lz_config* cfg, int32_t K, int64_t cap, lz_io_si
 lz_status lz_get_info(const lz_handle* h, lz_info* info) {
   if (!h || !info) return fail(LZ_ERR_INVALID, "handle/info is NULL");
   std::memset(info, 0, sizeof *info);
-  const SysDesc& d = h->desc;
+  const lz::SysInfo& d = *h->desc;
   info->state_dim = d.state_dim;
   info->action_dim = d.action_dim;
   info->obs_dim = d.obs_dim;
@@ -376,25 +350,18 @@ lz_status lz_get_info(const lz_handle* h, lz_info* info) {
   info->counts_steps = h->count_steps;
   // algorithmic HBM bytes per env per lz_step (what roofline.achieved counts):
   // sio = state planes read + written, io = actions + obs + reward + done
+  // (LORENZ3 float32: 24 + 41; LORENZ4: 64 + 37, no action; PMSM: 88 + 37)
   const int t = h->f64 ? 8 : 4;
-  int sio = 0, io = 0;
-  switch (h->cfg.system) {
-    case LZ_SYS_LORENZ3: sio = 2 * 3 * t; io = 3 * 4 + 6 * t + t + 1; break;  // 24 + 41 (f32)
-    case LZ_SYS_LORENZ4: sio = 2 * 8 * t; io = 8 * t + t + 1; break;          // 64 + 37, no act
-    case LZ_SYS_PMSM:  // s1,s2 + lambda,m,v + adam_step + current_step
-      sio = 2 * (6 * 4 + 3 * 4 + 4 + 4); io = 2 * 4 + 6 * 4 + 4 + 1; break;   // 88 + 37
-    case LZ_SYS_HR:
-      sio = 2 * 6 * t;
-      if (h->cfg.flags & LZ_FLAG_ADD_NOISE) sio += t;        // sigma read
-      if (h->cfg.flags & LZ_FLAG_ADD_FILTER) sio += 2 * 2 * 4;  // filtered_action
-      io = 2 * 4 + 6 * t + t + 1;
-      break;
-    case LZ_SYS_T1: sio = 2 * 3 * t; io = 2 * 4 + 6 * t + t + 1; break;
-    case LZ_SYS_T2: sio = 2 * 8 * t; io = 3 * 4 + 8 * t + t + 1; break;
-    case LZ_SYS_TP: sio = 2 * 6 * t; io = 2 * 4 + 6 * t + t + 1; break;
-    case LZ_SYS_SC: sio = 2 * 3 * t; io = 6 * t + t + 1; break;  // no action
-  }
-  if (h->count_steps && h->cfg.system != LZ_SYS_PMSM) sio += 8;
+  // every plane below the step plane is read and written each step (PMSM: s1, s2, lambda,
+  // m, v, adam_step) -- but for HR's sigma and filtered_action, which depend on the flags
+  const bool hr = h->cfg.system == LZ_SYS_HR;
+  int sio = 0;
+  for (int p = 0; p < (hr ? d.state_dim : d.step_plane); ++p) sio += 2 * plane_elem(d, h->f64, p);
+  if (hr && (h->cfg.flags & LZ_FLAG_ADD_NOISE)) sio += t;            // sigma read
+  if (hr && (h->cfg.flags & LZ_FLAG_ADD_FILTER)) sio += 2 * 2 * 4;   // filtered_action
+  // the step plane: PMSM's current_step always, the others' when the handle counts steps
+  if (h->count_steps || h->cfg.system == LZ_SYS_PMSM) sio += 8;
+  const int io = (d.uses_action ? d.action_dim * 4 : 0) + d.obs_dim * t + t + 1;
   const int b = sio + io;
   info->state_io_bytes = sio;
   info->bytes_per_env_step = b;
@@ -439,6 +406,9 @@ static int sys_key(const lz_handle* h) {
   return (h->cfg.integrator == LZ_INT_RK4 && (s == LZ_SYS_LORENZ3 || s == LZ_SYS_LORENZ4)) ? s + lz::kSysRK4
                                                                                             : s;
 }
+
+// step() reads the action: else the actions pointer may be NULL (LORENZ4, SC)
+static bool needs_act(const lz_handle* h) { return h->desc->uses_action; }
 
 static void fill_common(const lz_handle* h, KArgs& a) {
   std::memset(&a, 0, sizeof a);
@@ -489,8 +459,7 @@ lz_status lz_step(lz_handle* h, const void* actions, const double* noise, void* 
   RESIDENT_QUIESCE(h);
   if (!h->was_reset) return fail(LZ_ERR_STATE, "lz_step before the first lz_reset");
   // LORENZ4 ignores its action, SC takes none
-  const bool needs_act = h->cfg.system != LZ_SYS_LORENZ4 && h->cfg.system != LZ_SYS_SC;
-  if ((needs_act && !actions) || !obs_out || !rew_out || !done_out)
+  if ((needs_act(h) && !actions) || !obs_out || !rew_out || !done_out)
     return fail(LZ_ERR_INVALID, "actions/obs_out/rew_out/done_out must be non-NULL");
   if ((done_idx_out == nullptr) != (terminal_obs_out == nullptr))
     return fail(LZ_ERR_INVALID, "done_idx_out and terminal_obs_out go together");
@@ -506,7 +475,7 @@ lz_status lz_step(lz_handle* h, const void* actions, const double* noise, void* 
   a.term_obs = terminal_obs_out;
   // full 256-env blocks start at 256*A*4 / 256*O*sizeof(T) byte offsets: only the
   // base pointers need 16-B alignment (ragged tail blocks take the scalar path)
-  a.vec_ok = (!needs_act || aligned16(actions)) && aligned16(obs_out);
+  a.vec_ok = (!needs_act(h) || aligned16(actions)) && aligned16(obs_out);
   const int e = lz::launch_step(sys_key(h), h->f64, a, h->stream);
   if (e != 0) return fail(LZ_ERR_HIP, "step launch: %s", hipGetErrorString((hipError_t)e));
   if (n_done_out)
@@ -523,14 +492,13 @@ lz_status lz_step_host(lz_handle* h, const float* actions, const double* noise, 
   if (!h) return fail(LZ_ERR_INVALID, "handle is NULL");
   RESIDENT_QUIESCE(h);
   if (!h->was_reset) return fail(LZ_ERR_STATE, "lz_step_host before the first lz_reset");
-  const bool needs_act = h->cfg.system != LZ_SYS_LORENZ4 && h->cfg.system != LZ_SYS_SC;
-  if ((needs_act && !actions) || !obs_out || !rew_out || !done_out)
+  if ((needs_act(h) && !actions) || !obs_out || !rew_out || !done_out)
     return fail(LZ_ERR_INVALID, "actions/obs_out/rew_out/done_out must be non-NULL");
   HIP_TRY(hipSetDevice(h->cfg.device));
   const int64_t n = h->cfg.num_envs;
   const size_t es = h->f64 ? 8 : 4;
-  const size_t b_act = (size_t)n * h->desc.action_dim * 4, b_nz = (size_t)n * 3 * 8;
-  const size_t b_obs = (size_t)n * h->desc.obs_dim * es, b_rew = (size_t)n * es;
+  const size_t b_act = (size_t)n * h->desc->action_dim * 4, b_nz = (size_t)n * 3 * 8;
+  const size_t b_obs = (size_t)n * h->desc->obs_dim * es, b_rew = (size_t)n * es;
   const size_t o_nz = align16(b_act), in = align16(o_nz + b_nz);
   const size_t o_rew = align16(b_obs), o_done = align16(o_rew + b_rew), out = o_done + (size_t)n;
   if (!h->hs_pin) {
@@ -546,10 +514,10 @@ lz_status lz_step_host(lz_handle* h, const float* actions, const double* noise, 
     h->hs_in = in;
     h->hs_out = out;
   }
-  if (needs_act) std::memcpy(h->hs_pin, actions, b_act);
+  if (needs_act(h)) std::memcpy(h->hs_pin, actions, b_act);
   if (noise) std::memcpy(h->hs_pin + o_nz, noise, b_nz);
   uint8_t* d_out = h->hs_dev + in;
-  const lz_status st = lz_step(h, needs_act ? h->hs_dev : nullptr,
+  const lz_status st = lz_step(h, needs_act(h) ? h->hs_dev : nullptr,
                                noise ? reinterpret_cast<const double*>(h->hs_dev + o_nz) : nullptr,
                                d_out, d_out + o_rew, d_out + o_done, nullptr, nullptr, nullptr);
   if (st != LZ_OK) return st;
@@ -571,7 +539,7 @@ constexpr size_t kRsNoise = kRsAct + 64 * 4 * 4, kRsOut = kRsNoise + 64 * 3 * 8;
 constexpr int kRsMaxEnvs = 64;
 
 static size_t rs_rew_off(const lz_handle* h) {
-  return kRsOut + align16((size_t)h->cfg.num_envs * h->desc.obs_dim * (h->f64 ? 8 : 4));
+  return kRsOut + align16((size_t)h->cfg.num_envs * h->desc->obs_dim * (h->f64 ? 8 : 4));
 }
 static size_t rs_done_off(const lz_handle* h) {
   return rs_rew_off(h) + align16((size_t)h->cfg.num_envs * (h->f64 ? 8 : 4));
@@ -579,7 +547,7 @@ static size_t rs_done_off(const lz_handle* h) {
 static size_t rs_pub_stride(const lz_handle* h) { return align16((size_t)h->cfg.num_envs * 8); }
 static size_t rs_pub_off(const lz_handle* h) { return rs_done_off(h) + align16((size_t)h->cfg.num_envs); }
 static size_t rs_reply_off(const lz_handle* h) {
-  return (rs_pub_off(h) + (size_t)h->desc.n_planes * rs_pub_stride(h) + 63) & ~(size_t)63;
+  return (rs_pub_off(h) + (size_t)h->desc->n_planes * rs_pub_stride(h) + 63) & ~(size_t)63;
 }
 static size_t rs_bytes(const lz_handle* h) { return rs_reply_off(h) + lz::kRsReplyWords * 8; }
 
@@ -591,11 +559,11 @@ struct RsReplyLayout {
 };
 static int rs_reply_layout(const lz_handle* h, RsReplyLayout& L) {
   int c = 0;
-  const int O = h->desc.obs_dim;
+  const int O = h->desc->obs_dim;
   for (int p = 0; p < lz::kMaxPlanes; ++p) L.pub[p] = -1;
   for (int pass = 8; pass >= 4; pass -= 4) {
-    for (int p = 0; p < h->desc.n_planes; ++p)
-      if (plane_elem(h->cfg.system, h->f64, p) == pass) {
+    for (int p = 0; p < h->desc->n_planes; ++p)
+      if (plane_elem(*h->desc, h->f64, p) == pass) {
         L.pub[p] = c;
         c += pass / 4;
       }
@@ -657,8 +625,7 @@ static_assert(lz::kRsMaxHandles <= 16, "one request line per member in 1 KiB");
 constexpr uint64_t kRsStop = ~0ull;  // granule 0 of any line: every wave leaves
 
 static int rs_act_words(const lz_handle* h) {
-  const bool needs_act = h->cfg.system != LZ_SYS_LORENZ4 && h->cfg.system != LZ_SYS_SC;
-  return needs_act ? h->desc.action_dim : 0;
+  return needs_act(h) ? h->desc->action_dim : 0;
 }
 // data words of a request that travels inside its line (1 env: its actions, then its 3
 // float64 noise values as lo / hi halves), or -1 (the mailbox path)
@@ -784,9 +751,9 @@ static lz_status rs_server_launch(RsServer& sv) {
     box.obs = m->rs_dev + kRsOut;
     box.rew = m->rs_dev + rs_rew_off(m);
     box.done = m->rs_dev + rs_done_off(m);
-    for (int p = 0; p < m->desc.n_planes; ++p) {
+    for (int p = 0; p < m->desc->n_planes; ++p) {
       box.pub[p] = m->rs_dev + rs_pub_off(m) + (size_t)p * rs_pub_stride(m);
-      box.pub_es[p] = plane_elem(m->cfg.system, m->f64, p);
+      box.pub_es[p] = plane_elem(*m->desc, m->f64, p);
     }
     box.next = m->rs_seq + 1;  // the requester's pending request, the others' next one
     box.use_noise = m->rs_use_noise;
@@ -840,8 +807,7 @@ lz_status lz_resident_step(lz_handle* h, const float* actions, const double* noi
                            void* rew_out, uint8_t* done_out) {
   if (!h) return fail(LZ_ERR_INVALID, "handle is NULL");
   if (!h->was_reset) return fail(LZ_ERR_STATE, "lz_resident_step before the first lz_reset");
-  const bool needs_act = h->cfg.system != LZ_SYS_LORENZ4 && h->cfg.system != LZ_SYS_SC;
-  if ((needs_act && !actions) || !obs_out || !rew_out || !done_out)
+  if ((needs_act(h) && !actions) || !obs_out || !rew_out || !done_out)
     return fail(LZ_ERR_INVALID, "actions/obs_out/rew_out/done_out must be non-NULL");
   const int64_t n = h->cfg.num_envs;
   if (n > kRsMaxEnvs) return fail(LZ_ERR_UNSUPPORTED, "lz_resident_step: at most %d envs", kRsMaxEnvs);
@@ -903,7 +869,7 @@ lz_status lz_resident_step(lz_handle* h, const float* actions, const double* noi
     if (aw) std::memcpy(words, actions, (size_t)aw * 4);
     if (noise) std::memcpy(words + aw, noise, 3 * 8);  // little endian: lo, hi halves
   } else {        // the mailbox path: inputs there first, the line's command granule after
-    if (needs_act) std::memcpy(h->rs_pin + kRsAct, actions, (size_t)n * h->desc.action_dim * 4);
+    if (needs_act(h)) std::memcpy(h->rs_pin + kRsAct, actions, (size_t)n * h->desc->action_dim * 4);
     if (noise) std::memcpy(h->rs_pin + kRsNoise, noise, (size_t)n * 3 * 8);
   }
   for (int g = 0; g < lz::kRsLineWords; ++g) h->rs_line[g] = rs_granule(seq, words[g]);
@@ -951,13 +917,13 @@ lz_status lz_resident_step(lz_handle* h, const float* actions, const double* noi
   if (rep_mode) {
     std::memcpy(h->rs_rep, rwords, (size_t)rw * 4);
     lk.unlock();
-    std::memcpy(obs_out, rwords + L.obs, (size_t)h->desc.obs_dim * es);
+    std::memcpy(obs_out, rwords + L.obs, (size_t)h->desc->obs_dim * es);
     std::memcpy(rew_out, rwords + L.rew, es);
     *done_out = (uint8_t)rwords[L.done];
     return LZ_OK;
   }
   lk.unlock();
-  std::memcpy(obs_out, h->rs_pin + kRsOut, (size_t)n * h->desc.obs_dim * es);
+  std::memcpy(obs_out, h->rs_pin + kRsOut, (size_t)n * h->desc->obs_dim * es);
   std::memcpy(rew_out, h->rs_pin + rs_rew_off(h), (size_t)n * es);
   std::memcpy(done_out, h->rs_pin + rs_done_off(h), (size_t)n);
   return LZ_OK;
@@ -972,7 +938,7 @@ lz_status lz_resident_stop(lz_handle* h) {
 
 lz_status lz_resident_read_state(lz_handle* h, int32_t plane, void* host_dst) {
   if (!h || !host_dst) return fail(LZ_ERR_INVALID, "handle/host_dst is NULL");
-  const int es = plane_elem(h->cfg.system, h->f64, plane);
+  const int es = plane_elem(*h->desc, h->f64, plane);
   if (!es) return fail(LZ_ERR_INVALID, "invalid plane %d", plane);
   const size_t bytes = (size_t)h->cfg.num_envs * es;
   {
@@ -998,14 +964,14 @@ lz_status lz_resident_read_state(lz_handle* h, int32_t plane, void* host_dst) {
 static lz_status check_vecnorm(const lz_handle* h, const lz_vecnorm* vn) {
   if (!vn || !vn->obs_rms || !vn->ret_rms || !vn->returns)
     return fail(LZ_ERR_INVALID, "vecnorm: obs_rms/ret_rms/returns must be non-NULL");
-  if (lz::rms_dim(vn->obs_rms) != h->desc.obs_dim || lz::rms_dim(vn->ret_rms) != 1)
+  if (lz::rms_dim(vn->obs_rms) != h->desc->obs_dim || lz::rms_dim(vn->ret_rms) != 1)
     return fail(LZ_ERR_INVALID, "vecnorm: obs_rms dim %d (obs_dim %d), ret_rms dim %d (1)",
-                lz::rms_dim(vn->obs_rms), h->desc.obs_dim, lz::rms_dim(vn->ret_rms));
+                lz::rms_dim(vn->obs_rms), h->desc->obs_dim, lz::rms_dim(vn->ret_rms));
   if (lz::rms_device(vn->obs_rms) != h->cfg.device || lz::rms_device(vn->ret_rms) != h->cfg.device)
     return fail(LZ_ERR_INVALID, "vecnorm: statistics live on another device");
   if ((vn->flags & LZ_VN_DEFER) && !vn->moments)
     return fail(LZ_ERR_INVALID, "vecnorm: LZ_VN_DEFER needs moments");
-  if (h->desc.obs_dim > lz::kVnMaxObs) return fail(LZ_ERR_UNSUPPORTED, "vecnorm: obs too wide");
+  if (h->desc->obs_dim > lz::kVnMaxObs) return fail(LZ_ERR_UNSUPPORTED, "vecnorm: obs too wide");
   return LZ_OK;
 }
 
@@ -1017,8 +983,7 @@ lz_status lz_step_vecnorm(lz_handle* h, const lz_vecnorm* vn, const void* action
   if (!h->was_reset) return fail(LZ_ERR_STATE, "lz_step_vecnorm before the first lz_reset");
   const lz_status c = check_vecnorm(h, vn);
   if (c != LZ_OK) return c;
-  const bool needs_act = h->cfg.system != LZ_SYS_LORENZ4 && h->cfg.system != LZ_SYS_SC;
-  if ((needs_act && !actions) || !obs_out || !rew_out || !done_out || !done_idx_out ||
+  if ((needs_act(h) && !actions) || !obs_out || !rew_out || !done_out || !done_idx_out ||
       !terminal_obs_out || !n_done_out)
     return fail(LZ_ERR_INVALID, "actions/obs/rew/done/done_idx/terminal_obs/n_done must be non-NULL");
   HIP_TRY(hipSetDevice(h->cfg.device));
@@ -1039,7 +1004,7 @@ lz_status lz_step_vecnorm(lz_handle* h, const lz_vecnorm* vn, const void* action
   a.done = done_out;
   a.done_idx32 = done_idx_out;
   a.term_obs = terminal_obs_out;
-  a.vec_ok = (!needs_act || aligned16(actions)) && aligned16(obs_out);
+  a.vec_ok = (!needs_act(h) || aligned16(actions)) && aligned16(obs_out);
   lz::VArgs v;
   std::memset(&v, 0, sizeof v);
   v.returns = vn->returns;
@@ -1091,7 +1056,7 @@ lz_status lz_vecnorm_apply(lz_handle* h, const lz_vecnorm* vn, const void* obs_r
                               "(another launch on the handle came in between)");
   }
   HIP_TRY(hipSetDevice(h->cfg.device));
-  const int O = h->desc.obs_dim;
+  const int O = h->desc->obs_dim;
   if ((vn->flags & LZ_VN_DEFER) && (vn->flags & LZ_VN_TRAINING)) {
     int e = 0;
     if (vn->flags & LZ_VN_NORM_OBS) e = lz::launch_rms_update(vn->obs_rms, vn->moments, h->stream);
@@ -1135,8 +1100,7 @@ lz_status lz_rollout(lz_handle* h, int32_t K, const void* actions, void* obs_out
   RESIDENT_QUIESCE(h);
   if (!h->was_reset) return fail(LZ_ERR_STATE, "lz_rollout before the first lz_reset");
   if (K <= 0) return fail(LZ_ERR_INVALID, "K must be >= 1");
-  const bool needs_act = h->cfg.system != LZ_SYS_LORENZ4 && h->cfg.system != LZ_SYS_SC;
-  if ((needs_act && !actions) || !obs_out || !rew_out || !done_out)
+  if ((needs_act(h) && !actions) || !obs_out || !rew_out || !done_out)
     return fail(LZ_ERR_INVALID, "actions/obs_out/rew_out/done_out must be non-NULL");
   if ((done_idx_out == nullptr) != (terminal_obs_out == nullptr))
     return fail(LZ_ERR_INVALID, "done_idx_out and terminal_obs_out go together");
@@ -1153,7 +1117,7 @@ lz_status lz_rollout(lz_handle* h, int32_t K, const void* actions, void* obs_out
   a.term_cap = cap;
   a.K = K;
   a.tick_adv = (uint64_t)K;
-  a.vec_ok = (!needs_act || aligned16(actions)) && aligned16(obs_out) && (a.n % 4 == 0);
+  a.vec_ok = (!needs_act(h) || aligned16(actions)) && aligned16(obs_out) && (a.n % 4 == 0);
   const int e = lz::launch_rollout(sys_key(h), h->f64, a, h->stream);
   if (e != 0) return fail(LZ_ERR_HIP, "rollout launch: %s", hipGetErrorString((hipError_t)e));
   if (n_done_out)
@@ -1163,43 +1127,48 @@ lz_status lz_rollout(lz_handle* h, int32_t K, const void* actions, void* obs_out
   return LZ_OK;
 }
 
-// arch: 0 = MlpPolicy (bf16), 1 = attention extractor, 2 = residual + LayerNorm attention
-// on VecFrameStack(n_stack) observations, 3 = MlpPolicy in float32, 4 / 5 = arch 1 / 2 in
-// float32
-static lz_status rollout_policy(lz_handle* h, const lz_policy_rollout_args* r, int arch,
-                                int n_stack = 1, const float* stack_in = nullptr,
-                                float* stack_out = nullptr) {
-  if (!h || !r) return fail(LZ_ERR_INVALID, "handle/args is NULL");
-  RESIDENT_QUIESCE(h);
-  const bool attn = arch == 1 || arch == 2 || arch == 4 || arch == 5;
-  const bool stacked = arch == 2 || arch == 5;
-  if (stacked) {
-    if (n_stack != 1 && n_stack != 4) return fail(LZ_ERR_UNSUPPORTED, "n_stack must be 1 or 4");
-    if (!stack_in || !stack_out) return fail(LZ_ERR_INVALID, "stack_in / stack_out must be non-NULL");
-    if (r->obs_norm || r->obs_moments)
-      return fail(LZ_ERR_UNSUPPORTED, "the frame-stacked rollout takes no VecNormalize statistics");
-    const int sys = h->cfg.system;
-    if (sys != LZ_SYS_LORENZ3 && sys != LZ_SYS_PMSM && sys != LZ_SYS_HR)
-      return fail(LZ_ERR_UNSUPPORTED, "the frame-stacked rollout runs LORENZ3 / PMSM / HR");
-    if (n_stack * h->desc.obs_dim > lz::kLnMaxIn) return fail(LZ_ERR_UNSUPPORTED, "stacked obs > 32 dims");
-  }
-  if (arch == 4) {
-    const int sys = h->cfg.system;
-    if (sys != LZ_SYS_LORENZ3 && sys != LZ_SYS_PMSM && sys != LZ_SYS_HR)
-      return fail(LZ_ERR_UNSUPPORTED, "the float32 attention rollout runs LORENZ3 / PMSM / HR");
-  }
-  if ((r->flags & LZ_POLICY_I8X4) && arch < 3)
-    return fail(LZ_ERR_UNSUPPORTED, "LZ_POLICY_I8X4 runs the float32 (attention / MlpPolicy) rollouts only");
-  if ((r->flags & LZ_POLICY_I8X4) && arch == 3) {
-    const int sys = h->cfg.system;
-    if (sys != LZ_SYS_LORENZ3 && sys != LZ_SYS_LORENZ4 && sys != LZ_SYS_PMSM && sys != LZ_SYS_HR)
-      return fail(LZ_ERR_UNSUPPORTED, "the i8x4 MlpPolicy rollout runs LORENZ3 / LORENZ4 / PMSM / HR");
-  }
-  if (!h->was_reset) return fail(LZ_ERR_STATE, "lz_rollout_policy before the first lz_reset");
+// One row per policy rollout entry point: what rollout_policy launches and what
+// lz_get_launch_shape reports for it both come from here.
+struct PolicyRow {
+  lz::PolicyKind kind;
+  int32_t call;           // LZ_CALL_*
+  int32_t kernel;         // LZ_KERNEL_* (the MlpPolicy rows: refined by the shape, lz_get_launch_shape)
+  lz::PolShapeFn shape;
+  bool stacked;           // takes a VecFrameStack (n_stack, stack_in / stack_out)
+  bool i8x4;              // accepts LZ_POLICY_I8X4
+  const char* refusal;    // the message for a system the kind is not built for
+};
+const PolicyRow kPolicyTable[] = {  // indexed by PolicyKind
+    {lz::PolicyKind::Bf16Mlp, LZ_CALL_ROLLOUT_POLICY, LZ_KERNEL_POLICY, lz::policy_shape, false, false, ""},
+    {lz::PolicyKind::Bf16Attn, LZ_CALL_ROLLOUT_POLICY_ATTN, LZ_KERNEL_POLICY_ATTN, lz::attn_policy_shape, false,
+     false, ""},
+    {lz::PolicyKind::Bf16AttnLn, LZ_CALL_ROLLOUT_POLICY_ATTN_STACK, LZ_KERNEL_POLICY_ATTN, lz::attn_policy_shape,
+     true, false, "the frame-stacked rollout runs LORENZ3 / PMSM / HR"},
+    {lz::PolicyKind::F32Mlp, LZ_CALL_ROLLOUT_POLICY_F32, LZ_KERNEL_POLICY, lz::f32_policy_shape, false, true, ""},
+    {lz::PolicyKind::F32Attn, LZ_CALL_ROLLOUT_POLICY_ATTN_F32, LZ_KERNEL_POLICY_ATTN_F32,
+     lz::attn_f32_policy_shape, false, true, "the float32 attention rollout runs LORENZ3 / PMSM / HR"},
+    {lz::PolicyKind::F32AttnLn, LZ_CALL_ROLLOUT_POLICY_ATTN_STACK_F32, LZ_KERNEL_POLICY_ATTN_F32,
+     lz::attn_f32_policy_shape, true, true, "the frame-stacked rollout runs LORENZ3 / PMSM / HR"},
+    {lz::PolicyKind::F32MlpStep, LZ_CALL_POLICY_STEP_F32, LZ_KERNEL_POLICY_STEP, lz::f32_policy_shape, false,
+     false, ""},
+};
+static const PolicyRow& policy_row(lz::PolicyKind k) { return kPolicyTable[(int)k]; }
+static lz::PolShape policy_shape_of(const lz_handle* h, const PolicyRow& row) {
+  return row.shape(h->cfg.num_envs, h->num_cus, h->cfg.reserved[0]);
+}
+
+// The checks every policy entry point makes of the handle, then (after its own) of the
+// buffers; who: the entry point's name in the message
+static lz_status check_policy_handle(const lz_handle* h, const lz_policy_rollout_args* r, const char* who) {
+  if (!h->was_reset) return fail(LZ_ERR_STATE, "%s before the first lz_reset", who);
   if (h->f64) return fail(LZ_ERR_UNSUPPORTED, "the policy rollout runs float32 handles only");
   if (sys_key(h) != h->cfg.system)
     return fail(LZ_ERR_UNSUPPORTED, "the policy rollouts run the reference's Euler integrator only");
   if (r->K <= 0) return fail(LZ_ERR_INVALID, "K must be >= 1");
+  return LZ_OK;
+}
+
+static lz_status check_policy_buffers(const lz_handle* h, const lz_policy_rollout_args* r) {
   if (!r->blob || !r->obs_in || !r->obs_last || !r->obs_buf || !r->act_buf || !r->logp_buf ||
       !r->val_buf || !r->rew_buf || !r->done_buf || !r->last_values)
     return fail(LZ_ERR_INVALID, "blob / obs / rollout buffers must be non-NULL");
@@ -1207,24 +1176,11 @@ static lz_status rollout_policy(lz_handle* h, const lz_policy_rollout_args* r, i
     return fail(LZ_ERR_INVALID, "done_idx and terminal_obs go together");
   if ((int64_t)r->K * h->cfg.num_envs > ((int64_t)1 << 40)) return fail(LZ_ERR_INVALID, "K*N too large");
   if (!(r->act_low <= r->act_high)) return fail(LZ_ERR_INVALID, "act_low > act_high");
-  HIP_TRY(hipSetDevice(h->cfg.device));
-  const int64_t n = h->cfg.num_envs;
-  const lz::PolShape sh = arch >= 4   ? lz::attn_f32_policy_shape(n, h->num_cus, arch == 5)
-                         : attn      ? lz::attn_policy_shape(n, h->num_cus)
-                         : arch == 3 ? lz::f32_policy_shape(n, h->num_cus, h->cfg.reserved[0])
-                                     : lz::policy_shape(n, h->cfg.reserved[0], h->num_cus);
-  const int W = sh.waves, grid = sh.grid;
-  const int O = h->desc.obs_dim;
-  const int64_t need = (int64_t)grid * W * 2 * O;
-  if (r->obs_moments && h->pol_part_n < need) {
-    if (h->pol_part) HIP_TRY(hipFree(h->pol_part));
-    h->pol_part = nullptr;
-    h->pol_part_n = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&h->pol_part), (size_t)need * sizeof(double)) != hipSuccess)
-      return fail(LZ_ERR_OOM, "policy moment scratch allocation failed");
-    h->pol_part_n = need;
-  }
-  KArgs a;
+  return LZ_OK;
+}
+
+// the launch arguments every policy entry point fills from r (the rest stays zero)
+static void fill_policy_args(const lz_handle* h, const lz_policy_rollout_args* r, KArgs& a, lz::PArgs& p) {
   fill_common(h, a);
   a.obs = r->obs_buf;
   a.rew = r->rew_buf;
@@ -1233,8 +1189,6 @@ static lz_status rollout_policy(lz_handle* h, const lz_policy_rollout_args* r, i
   a.term_obs = r->terminal_obs;
   a.term_cap = r->cap;
   a.K = r->K;
-  a.tick_adv = (uint64_t)r->K;
-  lz::PArgs p;
   std::memset(&p, 0, sizeof p);
   p.blob = static_cast<const uint8_t*>(r->blob);
   p.obs_in = r->obs_in;
@@ -1250,15 +1204,52 @@ static lz_status rollout_policy(lz_handle* h, const lz_policy_rollout_args* r, i
   p.logp = r->logp_buf;
   p.val = r->val_buf;
   p.last_val = r->last_values;
+}
+
+static lz_status rollout_policy(lz_handle* h, const lz_policy_rollout_args* r, lz::PolicyKind kind,
+                                int n_stack = 1, const float* stack_in = nullptr,
+                                float* stack_out = nullptr) {
+  if (!h || !r) return fail(LZ_ERR_INVALID, "handle/args is NULL");
+  RESIDENT_QUIESCE(h);
+  const PolicyRow& row = policy_row(kind);
+  if (row.stacked) {
+    if (n_stack != 1 && n_stack != 4) return fail(LZ_ERR_UNSUPPORTED, "n_stack must be 1 or 4");
+    if (!stack_in || !stack_out) return fail(LZ_ERR_INVALID, "stack_in / stack_out must be non-NULL");
+    if (r->obs_norm || r->obs_moments)
+      return fail(LZ_ERR_UNSUPPORTED, "the frame-stacked rollout takes no VecNormalize statistics");
+  }
+  if (!(h->desc->policies & lz::pol_bit(kind))) return fail(LZ_ERR_UNSUPPORTED, "%s", row.refusal);
+  if (row.stacked && n_stack * h->desc->obs_dim > lz::kLnMaxIn)
+    return fail(LZ_ERR_UNSUPPORTED, "stacked obs > 32 dims");
+  if ((r->flags & LZ_POLICY_I8X4) && !row.i8x4)
+    return fail(LZ_ERR_UNSUPPORTED, "LZ_POLICY_I8X4 runs the float32 (attention / MlpPolicy) rollouts only");
+  if ((r->flags & LZ_POLICY_I8X4) && kind == lz::PolicyKind::F32Mlp && !(h->desc->policies & lz::kPolMlpI8))
+    return fail(LZ_ERR_UNSUPPORTED, "the i8x4 MlpPolicy rollout runs LORENZ3 / LORENZ4 / PMSM / HR");
+  lz_status cs = check_policy_handle(h, r, "lz_rollout_policy");
+  if (cs == LZ_OK) cs = check_policy_buffers(h, r);
+  if (cs != LZ_OK) return cs;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const int64_t n = h->cfg.num_envs;
+  const lz::PolShape sh = policy_shape_of(h, row);
+  const int W = sh.waves, grid = sh.grid;
+  const int O = h->desc->obs_dim;
+  const int64_t need = (int64_t)grid * W * 2 * O;
+  if (r->obs_moments && h->pol_part_n < need) {
+    if (h->pol_part) HIP_TRY(hipFree(h->pol_part));
+    h->pol_part = nullptr;
+    h->pol_part_n = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&h->pol_part), (size_t)need * sizeof(double)) != hipSuccess)
+      return fail(LZ_ERR_OOM, "policy moment scratch allocation failed");
+    h->pol_part_n = need;
+  }
+  KArgs a;
+  lz::PArgs p;
+  fill_policy_args(h, r, a, p);
+  a.tick_adv = (uint64_t)r->K;
   p.partials = r->obs_moments ? h->pol_part : nullptr;
   p.stack_in = stack_in;
   p.stack_out = stack_out;
-  int e = arch >= 4 ? lz::launch_rollout_policy_attn_f32(h->cfg.system, arch == 5, n_stack, a, p, sh,
-                                                        h->stream)
-          : arch == 2 ? lz::launch_rollout_policy_attn_ln(h->cfg.system, n_stack, a, p, sh, h->stream)
-          : arch == 1 ? lz::launch_rollout_policy_attn(h->cfg.system, a, p, sh, h->stream)
-          : arch == 3 ? lz::launch_rollout_policy_f32(h->cfg.system, a, p, sh, h->stream)
-                      : lz::launch_rollout_policy(h->cfg.system, a, p, sh, h->stream);
+  int e = lz::launch_policy(kind, h->cfg.system, n_stack, a, p, nullptr, sh, h->stream);
   if (e != 0) return fail(LZ_ERR_HIP, "policy rollout launch: %s", hipGetErrorString((hipError_t)e));
   if (r->obs_moments) {
     e = lz::launch_policy_moments_final(h->pol_part, grid * W, 2 * O, (double)r->K * (double)n,
@@ -1273,15 +1264,15 @@ static lz_status rollout_policy(lz_handle* h, const lz_policy_rollout_args* r, i
 }
 
 lz_status lz_rollout_policy(lz_handle* h, const lz_policy_rollout_args* r) {
-  return rollout_policy(h, r, 0);
+  return rollout_policy(h, r, lz::PolicyKind::Bf16Mlp);
 }
 
 lz_status lz_rollout_policy_f32(lz_handle* h, const lz_policy_rollout_args* r) {
-  return rollout_policy(h, r, 3);
+  return rollout_policy(h, r, lz::PolicyKind::F32Mlp);
 }
 
 lz_status lz_rollout_policy_attn(lz_handle* h, const lz_policy_rollout_args* r) {
-  return rollout_policy(h, r, 1);
+  return rollout_policy(h, r, lz::PolicyKind::Bf16Attn);
 }
 
 // ---- SB3-exact VecNormalize in the float32 rollout (lz_internal.h PStepArgs)
@@ -1291,24 +1282,16 @@ lz_status lz_policy_step_f32(lz_handle* h, const lz_policy_rollout_args* r, int3
   RESIDENT_QUIESCE(h);
   if (r->flags & LZ_POLICY_I8X4)
     return fail(LZ_ERR_UNSUPPORTED, "LZ_POLICY_I8X4 runs the float32 rollouts only, not the per-step collect");
-  if (!h->was_reset) return fail(LZ_ERR_STATE, "lz_policy_step_f32 before the first lz_reset");
-  if (h->f64) return fail(LZ_ERR_UNSUPPORTED, "the policy rollout runs float32 handles only");
-  if (sys_key(h) != h->cfg.system)
-    return fail(LZ_ERR_UNSUPPORTED, "the policy rollouts run the reference's Euler integrator only");
-  if (r->K <= 0) return fail(LZ_ERR_INVALID, "K must be >= 1");
+  lz_status cs = check_policy_handle(h, r, "lz_policy_step_f32");
+  if (cs != LZ_OK) return cs;
   if (k < 0 || k > r->K) return fail(LZ_ERR_INVALID, "step %d outside [0, K = %d]", k, r->K);
   if (!obs_rms_state) return fail(LZ_ERR_INVALID, "obs_rms_state must be non-NULL");
   if (r->obs_norm && r->obs_norm != obs_rms_state)
     return fail(LZ_ERR_INVALID, "obs_norm must be NULL or obs_rms_state");
   if (r->obs_moments) return fail(LZ_ERR_INVALID, "obs_moments must be NULL (per-step statistics)");
-  if (!r->blob || !r->obs_in || !r->obs_last || !r->obs_buf || !r->act_buf || !r->logp_buf ||
-      !r->val_buf || !r->rew_buf || !r->done_buf || !r->last_values)
-    return fail(LZ_ERR_INVALID, "blob / obs / rollout buffers must be non-NULL");
-  if ((r->done_idx == nullptr) != (r->terminal_obs == nullptr))
-    return fail(LZ_ERR_INVALID, "done_idx and terminal_obs go together");
-  if ((int64_t)r->K * h->cfg.num_envs > ((int64_t)1 << 40)) return fail(LZ_ERR_INVALID, "K*N too large");
-  if (!(r->act_low <= r->act_high)) return fail(LZ_ERR_INVALID, "act_low > act_high");
-  const int O = h->desc.obs_dim;
+  cs = check_policy_buffers(h, r);
+  if (cs != LZ_OK) return cs;
+  const int O = h->desc->obs_dim;
   if (O > lz::kVnMaxObs) return fail(LZ_ERR_UNSUPPORTED, "obs too wide");
   HIP_TRY(hipSetDevice(h->cfg.device));
   const int64_t n = h->cfg.num_envs;
@@ -1342,35 +1325,14 @@ lz_status lz_policy_step_f32(lz_handle* h, const lz_policy_rollout_args* r, int3
   }
   const bool fin = k == r->K;
   if (k == 0) HIP_TRY(hipMemsetAsync(h->ps_cursor, 0, 2 * sizeof(int32_t), h->stream));
-  const lz::PolShape sh = lz::f32_policy_shape(n, h->num_cus, h->cfg.reserved[0]);
+  const lz::PolShape sh = policy_shape_of(h, policy_row(lz::PolicyKind::F32MlpStep));
   KArgs a;
-  fill_common(h, a);
-  a.obs = r->obs_buf;
-  a.rew = r->rew_buf;
-  a.done = r->done_buf;
-  a.done_idx64 = r->done_idx;
-  a.term_obs = r->terminal_obs;
-  a.term_cap = r->cap;
-  a.K = r->K;
+  lz::PArgs p;
+  fill_policy_args(h, r, a, p);
   a.counter = h->ps_cursor;       // one cursor for the whole collect (zeroed at k = 0)
   // a step launch flips the parity (below): it zeroes the cursor slot the handle's next
   // ordinary launch reads, as every other launch does (fill_common's counter_next)
-  lz::PArgs p;
-  std::memset(&p, 0, sizeof p);
-  p.blob = static_cast<const uint8_t*>(r->blob);
-  p.obs_in = r->obs_in;
-  p.obs_last = r->obs_last;
   p.norm = obs_rms_state;
-  p.eps = r->norm_eps;
-  p.clip = r->clip_obs;
-  p.gamma = (float)r->gamma;
-  p.act_lo = r->act_low;
-  p.act_hi = r->act_high;
-  p.pflags = r->flags;
-  p.act = r->act_buf;
-  p.logp = r->logp_buf;
-  p.val = r->val_buf;
-  p.last_val = r->last_values;
   lz::PStepArgs st;
   std::memset(&st, 0, sizeof st);
   st.k = k;
@@ -1380,7 +1342,7 @@ lz_status lz_policy_step_f32(lz_handle* h, const lz_policy_rollout_args* r, int3
   st.snap = fin ? nullptr : h->ps_tiles + 2 * O * ntiles;
   st.term = h->ps_term;
   st.obs_src = k == 0 ? r->obs_in : r->obs_last;
-  int e = lz::launch_policy_step_f32(h->cfg.system, a, p, st, sh, h->stream);
+  int e = lz::launch_policy(lz::PolicyKind::F32MlpStep, h->cfg.system, 1, a, p, &st, sh, h->stream);
   if (e != 0) return fail(LZ_ERR_HIP, "policy step launch: %s", hipGetErrorString((hipError_t)e));
   if (!fin) {
     h->parity ^= 1;  // the launch advanced the RNG tick by one (ping-pong)
@@ -1410,16 +1372,16 @@ lz_status lz_rollout_policy_f32_vn(lz_handle* h, const lz_policy_rollout_args* r
 
 lz_status lz_rollout_policy_attn_stack(lz_handle* h, const lz_policy_rollout_args* r,
                                        int32_t n_stack, const float* stack_in, float* stack_out) {
-  return rollout_policy(h, r, 2, n_stack, stack_in, stack_out);
+  return rollout_policy(h, r, lz::PolicyKind::Bf16AttnLn, n_stack, stack_in, stack_out);
 }
 
 lz_status lz_rollout_policy_attn_f32(lz_handle* h, const lz_policy_rollout_args* r) {
-  return rollout_policy(h, r, 4);
+  return rollout_policy(h, r, lz::PolicyKind::F32Attn);
 }
 
 lz_status lz_rollout_policy_attn_stack_f32(lz_handle* h, const lz_policy_rollout_args* r,
                                            int32_t n_stack, const float* stack_in, float* stack_out) {
-  return rollout_policy(h, r, 5, n_stack, stack_in, stack_out);
+  return rollout_policy(h, r, lz::PolicyKind::F32AttnLn, n_stack, stack_in, stack_out);
 }
 
 lz_status lz_get_launch_shape(const lz_handle* h, int32_t call, lz_launch_shape* out) {
@@ -1433,50 +1395,32 @@ lz_status lz_get_launch_shape(const lz_handle* h, int32_t call, lz_launch_shape*
     // leaves it NULL, the device-drawn case; LZ_CALL_STEP_NOISE asks for the injected one
     static const double kNoiseTag = 0.0;
     if (call == LZ_CALL_STEP_NOISE) a.noise = &kNoiseTag;
-    int32_t o[5] = {0, 0, 0, 0, 0};
-    if (lz::env_launch_shape(call == LZ_CALL_ROLLOUT ? 2 : 1, sys_key(h), h->f64, a, o) != 0)
+    lz::EnvShape o = {};
+    const lz::EnvLaunch which = call == LZ_CALL_ROLLOUT ? lz::EnvLaunch::Rollout : lz::EnvLaunch::Step;
+    if (lz::env_launch_shape(which, sys_key(h), h->f64, a, o) != 0)
       return fail(LZ_ERR_INVALID, "no launch shape for system %d", h->cfg.system);
-    out->kernel = o[0];
-    out->envs_per_wave = o[1];
-    out->waves = o[2];
-    out->grid = o[3];
-    out->flags = (uint32_t)o[4];
-    out->groups = o[3];
+    out->kernel = o.kernel;
+    out->envs_per_wave = o.envs_per_wave;
+    out->waves = o.waves;
+    out->grid = o.grid;
+    out->flags = o.flags;
+    out->groups = o.grid;
     return LZ_OK;
   }
-  lz::PolShape sh;
-  switch (call) {
-    case LZ_CALL_ROLLOUT_POLICY:
-      sh = lz::policy_shape(n, h->cfg.reserved[0], h->num_cus);
-      out->kernel = sh.envs_per_wave == 64 ? LZ_KERNEL_POLICY
-                    : sh.pair == 2         ? LZ_KERNEL_POLICY_PAIR_PIPE
-                    : sh.pair              ? LZ_KERNEL_POLICY_PAIR
-                                           : LZ_KERNEL_POLICY;
-      break;
-    case LZ_CALL_ROLLOUT_POLICY_F32:
-      sh = lz::f32_policy_shape(n, h->num_cus, h->cfg.reserved[0]);
-      out->kernel = sh.pair == 1 ? LZ_KERNEL_POLICY_SPLIT : LZ_KERNEL_POLICY;
-      break;
-    case LZ_CALL_POLICY_STEP_F32:
-      sh = lz::f32_policy_shape(n, h->num_cus, h->cfg.reserved[0]);
-      out->kernel = LZ_KERNEL_POLICY_STEP;
-      break;
-    case LZ_CALL_ROLLOUT_POLICY_ATTN:
-    case LZ_CALL_ROLLOUT_POLICY_ATTN_STACK:
-      sh = lz::attn_policy_shape(n, h->num_cus);
-      out->kernel = LZ_KERNEL_POLICY_ATTN;
-      break;
-    case LZ_CALL_ROLLOUT_POLICY_ATTN_F32:
-    case LZ_CALL_ROLLOUT_POLICY_ATTN_STACK_F32:
-      sh = lz::attn_f32_policy_shape(n, h->num_cus, call == LZ_CALL_ROLLOUT_POLICY_ATTN_STACK_F32);
-      out->kernel = LZ_KERNEL_POLICY_ATTN_F32;
-      break;
-    default:
-      return fail(LZ_ERR_INVALID, "unknown call %d", call);
+  const PolicyRow* row = nullptr;
+  for (const PolicyRow& c : kPolicyTable)
+    if (c.call == call) row = &c;
+  if (!row) return fail(LZ_ERR_INVALID, "unknown call %d", call);
+  const lz::PolShape sh = policy_shape_of(h, *row);
+  out->kernel = row->kernel;
+  out->waves = sh.waves;
+  if (row->kind == lz::PolicyKind::Bf16Mlp && sh.envs_per_wave != 64 && sh.pair)  // launch_pol
+    out->kernel = sh.pair == 2 ? LZ_KERNEL_POLICY_PAIR_PIPE : LZ_KERNEL_POLICY_PAIR;
+  if (row->kind == lz::PolicyKind::F32Mlp && sh.pair == 1) {  // launch_pol_f32_k
+    out->kernel = LZ_KERNEL_POLICY_SPLIT;
+    out->waves = 8;  // the split kernel runs 4 tiles per workgroup on 8 waves (actor + critic per tile)
   }
   out->envs_per_wave = sh.envs_per_wave;
-  // the split kernel runs 4 tiles per workgroup on 8 waves (actor + critic per tile)
-  out->waves = (call == LZ_CALL_ROLLOUT_POLICY_F32 && sh.pair == 1) ? 8 : sh.waves;
   out->grid = sh.grid;
   const int64_t groups = ((n + sh.envs_per_wave - 1) / sh.envs_per_wave + sh.waves - 1) / sh.waves;
   out->groups = (int32_t)groups;
@@ -1486,13 +1430,13 @@ lz_status lz_get_launch_shape(const lz_handle* h, int32_t call, lz_launch_shape*
 
 int32_t lz_plane_elem_size(const lz_handle* h, int32_t plane) {
   if (!h) return 0;
-  return plane_elem(h->cfg.system, h->f64, plane);
+  return plane_elem(*h->desc, h->f64, plane);
 }
 
 static lz_status plane_access(lz_handle* h, int32_t plane, void* buf, const int64_t* indices, int64_t count,
                               bool set) {
   if (!h || !buf) return fail(LZ_ERR_INVALID, "handle/%s is NULL", set ? "src" : "dst");
-  const int es = plane_elem(h->cfg.system, h->f64, plane);
+  const int es = plane_elem(*h->desc, h->f64, plane);
   if (!es) return fail(LZ_ERR_INVALID, "invalid plane %d", plane);
   if (!indices && count != 0 && count != h->cfg.num_envs)
     return fail(LZ_ERR_INVALID, "whole-plane access (indices NULL) with count %lld != 0 / num_envs",

@@ -372,10 +372,47 @@ int launch_vn_apply(int f64, int O, int64_t n, const void* obs, const void* rew,
 // SysL4RK4, lz_systems.h), else lz_config.system.
 constexpr int kSysRK4 = 256;
 
+// The policy-in-the-loop rollouts: one kind per entry point (lz_api.cpp kPolicyTable).
+enum class PolicyKind {
+  Bf16Mlp,       // lz_rollout_policy
+  Bf16Attn,      // lz_rollout_policy_attn
+  Bf16AttnLn,    // lz_rollout_policy_attn_stack (residual + LayerNorm, VecFrameStack)
+  F32Mlp,        // lz_rollout_policy_f32
+  F32Attn,       // lz_rollout_policy_attn_f32
+  F32AttnLn,     // lz_rollout_policy_attn_stack_f32
+  F32MlpStep,    // lz_policy_step_f32: F32Mlp one step per launch (SB3-exact VecNormalize)
+};
+constexpr unsigned pol_bit(PolicyKind k) { return 1u << (int)k; }
+// which kinds are built for a system (lz_dispatch.h for_system): every system runs the
+// MlpPolicy rollouts and the bf16 attention extractor; the frame-stacked and the float32
+// attention rollouts are built for the systems the reference trains them on (code/train.py
+// and lorenz_filter/train.py: HR) plus LORENZ3 / PMSM; kPolMlpI8: LZ_POLICY_I8X4 in the
+// F32Mlp rollout, built for the four systems of the reference's training scripts
+constexpr unsigned kPolBasic = pol_bit(PolicyKind::Bf16Mlp) | pol_bit(PolicyKind::Bf16Attn) |
+                               pol_bit(PolicyKind::F32Mlp) | pol_bit(PolicyKind::F32MlpStep);
+constexpr unsigned kPolAll = kPolBasic | pol_bit(PolicyKind::Bf16AttnLn) | pol_bit(PolicyKind::F32Attn) |
+                             pol_bit(PolicyKind::F32AttnLn);
+constexpr unsigned kPolMlpI8 = 1u << 16;
+
+// Host-side facts of a system, read off its Sys type (lz_systems.h) through the system
+// list (lz_dispatch.h sys_info_of)
+struct SysInfo {
+  int state_dim, action_dim, obs_dim, init_dim, n_planes;
+  int step_plane;
+  int t_planes;       // planes [0, t_planes) hold the handle's dtype, the rest 4-byte words
+  bool uses_action;   // step() reads the action (else the actions pointer may be NULL)
+  bool noise;
+  bool has_f64;       // a float64 instantiation exists
+  unsigned policies;  // kPol*
+};
+// system: lz_config.system; an all-zero entry for an unknown one (lz_kernels.hip)
+const SysInfo& sys_info(int system);
+
 // record the thread-local message lz_last_error() returns; returns s
 lz_status set_error(lz_status s, const char* msg);
 
 // host-side launchers (lz_kernels.hip)
+enum class EnvLaunch { Reset, Step, Rollout };
 int launch_reset(int system, int f64, const KArgs& a, void* stream);
 int launch_step(int system, int f64, const KArgs& a, void* stream);
 
@@ -445,9 +482,12 @@ struct ResMember {      // one wave of the server
 int launch_resident_multi(const ResMember* table, int n, const uint64_t* lines, uint64_t idle_ticks,
                           void* stream);
 int launch_rollout(int system, int f64, const KArgs& a, void* stream);
-// lz_get_launch_shape of lz_step (which = 1) / lz_rollout (which = 2): out[5] = kernel,
-// envs per wave, waves per workgroup, workgroups, flags
-int env_launch_shape(int which, int system, int f64, const KArgs& a, int32_t* out);
+// lz_get_launch_shape of lz_step (EnvLaunch::Step) / lz_rollout (EnvLaunch::Rollout)
+struct EnvShape {
+  int32_t kernel, envs_per_wave, waves, grid;  // LZ_KERNEL_*, ..., waves per workgroup, workgroups
+  uint32_t flags;                              // LZ_SHAPE_*
+};
+int env_launch_shape(EnvLaunch which, int system, int f64, const KArgs& a, EnvShape& out);
 // gather (scatter = false: buf[i] = plane[idx[i]]) / scatter (plane[idx[i]] = buf[i]) of
 // es-byte elements; indices outside [0, n) skipped / read as zero
 int launch_plane_index(bool scatter, int es, void* plane, int64_t n, const int64_t* idx, int64_t count,
@@ -470,7 +510,9 @@ int launch_step_vecnorm(int system, int f64, const KArgs& a, const VArgs& v, voi
 struct PolShape {
   int envs_per_wave, waves, pair, grid;
 };
-inline PolShape policy_shape(int64_t n, int variant, int num_cus) {
+// every shape function: (envs, compute units, lz_config.reserved[0])
+typedef PolShape (*PolShapeFn)(int64_t n, int num_cus, int variant);
+inline PolShape policy_shape(int64_t n, int num_cus, int variant) {
   PolShape s;
   const int64_t waves32 = (n + 31) / 32;
   if (variant & 32) s = {32, 8, 0, 0};
@@ -481,33 +523,24 @@ inline PolShape policy_shape(int64_t n, int variant, int num_cus) {
   s.grid = (int)(groups < num_cus ? groups : num_cus);
   return s;
 }
-int launch_rollout_policy(int system, const KArgs& a, const PArgs& p, const PolShape& sh,
-                          void* stream);
 // the float32 MlpPolicy (kF32* blob): 32 envs per wave, 8 waves (two per SIMD; the
 // 146 KB blob leaves room for one workgroup per CU, the obs moments live in registers);
 // below 8 tiles per CU 4 tiles per workgroup on 8 waves, the pi net and the env step in
 // waves 0-3, the value net in waves 4-7 (pair = 1); the per-step kernel runs 4 waves there
 PolShape f32_policy_shape(int64_t n, int num_cus, int variant);
-int launch_rollout_policy_f32(int system, const KArgs& a, const PArgs& p, const PolShape& sh,
-                              void* stream);
-// SB3-exact VecNormalize: one step of the float32 policy rollout (PStepArgs above)
-int launch_policy_step_f32(int system, const KArgs& a, const PArgs& p, const PStepArgs& s,
-                           const PolShape& sh, void* stream);
-// the attention-extractor policy (kAtt* blob): one shape, 32 envs per wave, 4 waves
+// the attention-extractor policy (kAtt* blob) and the residual + LayerNorm extractor on
+// VecFrameStack(n_stack = 1 or 4) obs (kLn* blob): one shape, 32 envs per wave, 4 waves
 // (one per SIMD: the 137 KB blob leaves room for one workgroup per CU)
-PolShape attn_policy_shape(int64_t n, int num_cus);
-int launch_rollout_policy_attn(int system, const KArgs& a, const PArgs& p, const PolShape& sh,
-                               void* stream);
-// the residual + LayerNorm extractor on VecFrameStack(n_stack) obs (kLn* blob);
-// n_stack 1 or 4, same shape as attn_policy_shape
-int launch_rollout_policy_attn_ln(int system, int n_stack, const KArgs& a, const PArgs& p,
-                                  const PolShape& sh, void* stream);
-// the attention actor-critics in float32 (kAF* blob): ln = 0 code/train.py's extractor,
-// 1 the residual + LayerNorm variant on VecFrameStack(n_stack = 1 or 4); systems LORENZ3 /
-// PMSM / HR; attn_f32_policy_shape's grid (16 envs per wave, 8 or 4 waves)
-PolShape attn_f32_policy_shape(int64_t n, int num_cus, int ln);
-int launch_rollout_policy_attn_f32(int system, int ln, int n_stack, const KArgs& a, const PArgs& p,
-                                   const PolShape& sh, void* stream);
+PolShape attn_policy_shape(int64_t n, int num_cus, int variant);
+// the attention actor-critics in float32 (kAF* blob), code/train.py's extractor and the
+// residual + LayerNorm variant alike: 16 envs per wave, 8 or 4 waves
+PolShape attn_f32_policy_shape(int64_t n, int num_cus, int variant);
+// Launch the rollout of `kind` for `system` (lz_config.system: the Euler systems);
+// hipErrorInvalidValue where the kind (or LZ_POLICY_I8X4 in F32Mlp) is not built for the
+// system (SysInfo::policies) or n_stack is not 1 or 4.  n_stack: the *AttnLn kinds';
+// st: F32MlpStep's (PStepArgs above), else nullptr.
+int launch_policy(PolicyKind kind, int system, int n_stack, const KArgs& a, const PArgs& p,
+                  const PStepArgs* st, const PolShape& sh, void* stream);
 int launch_policy_moments_final(const double* partials, int nparts, int width, double count,
                                 double* out, void* stream);
 

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "lz_body.h"
+#include "lz_dispatch.h"
 #include "lz_internal.h"
 #include "lz_rms_math.h"
 #include "lz_systems.h"
@@ -1369,10 +1370,10 @@ static void launch_rollout_d(const KArgs& a, hipStream_t s) {
 // kVariants: instantiate the step-kernel tuning variants (A/B tools use LORENZ3 and
 // PMSM; the other systems always run the default variant)
 template <class Sys, typename T, bool kVariants = false>
-static int launch_all(int which, const KArgs& a, hipStream_t s) {
+static int launch_all(EnvLaunch which, const KArgs& a, hipStream_t s) {
   const dim3 grid((unsigned)grid_for(a.n)), block(kBlock);
-  const int tiles = which == 1 && multi_step_ok<Sys>::value ? step_tiles<Sys>(a) : 1;
-  if (which == 0)
+  const int tiles = which == EnvLaunch::Step && multi_step_ok<Sys>::value ? step_tiles<Sys>(a) : 1;
+  if (which == EnvLaunch::Reset)
     hipLaunchKernelGGL((k_reset<Sys, T>), grid, block, 0, s, a);
   else if (tiles > 1) {
     if constexpr (multi_step_ok<Sys>::value) {
@@ -1383,9 +1384,9 @@ static int launch_all(int which, const KArgs& a, hipStream_t s) {
         hipLaunchKernelGGL((k_step_multi<Sys, T, 4, true>), g, block, 0, s, a);
       else hipLaunchKernelGGL((k_step_multi<Sys, T, 4>), g, block, 0, s, a);
     }
-  } else if (which == 1 && !kVariants) {
+  } else if (which == EnvLaunch::Step && !kVariants) {
     hipLaunchKernelGGL((k_step<Sys, T, 0>), grid, block, 0, s, a);
-  } else if (which == 1) {
+  } else if (which == EnvLaunch::Step) {
     switch (a.variant & 63) {
 #define LZ_STEP_V(VV)                                                                   \
   case VV:                                                                              \
@@ -1410,40 +1411,13 @@ static int launch_all(int which, const KArgs& a, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-static int dispatch(int which, int system, int f64, const KArgs& a, void* stream) {
+static int dispatch(EnvLaunch which, int system, int f64, const KArgs& a, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (system) {
-    case LZ_SYS_LORENZ3:
-      return f64 ? launch_all<SysL3<double>, double>(which, a, s)
-                 : launch_all<SysL3<float>, float, true>(which, a, s);
-    case LZ_SYS_LORENZ4:
-      return f64 ? launch_all<SysL4<double>, double>(which, a, s)
-                 : launch_all<SysL4<float>, float>(which, a, s);
-    case LZ_SYS_LORENZ3 + kSysRK4:
-      return f64 ? launch_all<SysL3RK4<double>, double>(which, a, s)
-                 : launch_all<SysL3RK4<float>, float>(which, a, s);
-    case LZ_SYS_LORENZ4 + kSysRK4:
-      return f64 ? launch_all<SysL4RK4<double>, double>(which, a, s)
-                 : launch_all<SysL4RK4<float>, float>(which, a, s);
-    case LZ_SYS_PMSM:
-      return launch_all<SysPMSM, float, true>(which, a, s);
-    case LZ_SYS_HR:
-      return f64 ? launch_all<SysHR<double>, double>(which, a, s)
-                 : launch_all<SysHR<float>, float>(which, a, s);
-    case LZ_SYS_T1:
-      return f64 ? launch_all<SysT1<double>, double>(which, a, s)
-                 : launch_all<SysT1<float>, float>(which, a, s);
-    case LZ_SYS_T2:
-      return f64 ? launch_all<SysT2<double>, double>(which, a, s)
-                 : launch_all<SysT2<float>, float>(which, a, s);
-    case LZ_SYS_TP:
-      return f64 ? launch_all<SysTP<double>, double>(which, a, s)
-                 : launch_all<SysTP<float>, float>(which, a, s);
-    case LZ_SYS_SC:
-      return f64 ? launch_all<SysSC<double>, double>(which, a, s)
-                 : launch_all<SysSC<float>, float>(which, a, s);
-  }
-  return (int)hipErrorInvalidValue;
+  return for_system(system, f64 != 0, [&](auto tag) {
+    using Sys = typename decltype(tag)::Sys;
+    constexpr bool kVariants = std::is_same<Sys, SysL3<float>>::value || std::is_same<Sys, SysPMSM>::value;
+    return launch_all<Sys, typename decltype(tag)::T, kVariants>(which, a, s);
+  });
 }
 
 // ------------------------------------------------------------------ launch shapes
@@ -1451,46 +1425,47 @@ static int dispatch(int which, int system, int f64, const KArgs& a, void* stream
 // envs per wave, waves per workgroup, workgroups, flags (lorenz_env.h LZ_KERNEL_* /
 // LZ_SHAPE_*) -- the same decisions launch_all / launch_rollout_d take.
 template <class Sys, typename T>
-static int env_shape_t(int which, const KArgs& a, int32_t* o) {
-  if (which == 1) {
+static int env_shape_t(EnvLaunch which, const KArgs& a, EnvShape& o) {
+  if (which == EnvLaunch::Step) {
     const int tiles = multi_step_ok<Sys>::value ? step_tiles<Sys>(a) : 1;
     const int64_t per = (int64_t)kBlock * tiles;
-    o[0] = tiles > 1 ? LZ_KERNEL_STEP_MULTI : LZ_KERNEL_STEP;
-    o[1] = 64;
-    o[2] = kBlock / 64;
-    o[3] = (int32_t)((a.n + per - 1) / per);
-    o[4] = 0;
+    o.kernel = tiles > 1 ? LZ_KERNEL_STEP_MULTI : LZ_KERNEL_STEP;
+    o.envs_per_wave = 64;
+    o.waves = kBlock / 64;
+    o.grid = (int32_t)((a.n + per - 1) / per);
+    o.flags = 0;
     return 0;
   }
   const RolloutPlan p = rollout_plan<Sys>(a);
-  o[0] = p.kind == 0   ? LZ_KERNEL_ROLLOUT
-         : p.kind == 1 ? LZ_KERNEL_ROLLOUT_WAVE
-         : p.kind == 2 ? LZ_KERNEL_ROLLOUT_SPLIT
-                       : LZ_KERNEL_ROLLOUT_PAIR;
-  o[1] = p.kind >= 2 ? 32 : 64;
-  o[2] = p.kind == 0 ? kBlock / 64 : p.np ? 2 : 1;
+  o.kernel = p.kind == 0   ? LZ_KERNEL_ROLLOUT
+             : p.kind == 1 ? LZ_KERNEL_ROLLOUT_WAVE
+             : p.kind == 2 ? LZ_KERNEL_ROLLOUT_SPLIT
+                           : LZ_KERNEL_ROLLOUT_PAIR;
+  o.envs_per_wave = p.kind >= 2 ? 32 : 64;
+  o.waves = p.kind == 0 ? kBlock / 64 : p.np ? 2 : 1;
   const int64_t per = p.kind == 0 ? kBlock : p.kind == 1 ? 64 : 32;
-  o[3] = (int32_t)((a.n + per - 1) / per);
-  o[4] = p.no_done ? LZ_SHAPE_NO_DONE : 0;
+  o.grid = (int32_t)((a.n + per - 1) / per);
+  o.flags = p.no_done ? LZ_SHAPE_NO_DONE : 0;
   return 0;
 }
 
-int env_launch_shape(int which, int system, int f64, const KArgs& a, int32_t* o) {
-  switch (system) {
-    case LZ_SYS_LORENZ3: return f64 ? env_shape_t<SysL3<double>, double>(which, a, o) : env_shape_t<SysL3<float>, float>(which, a, o);
-    case LZ_SYS_LORENZ4: return f64 ? env_shape_t<SysL4<double>, double>(which, a, o) : env_shape_t<SysL4<float>, float>(which, a, o);
-    case LZ_SYS_LORENZ3 + kSysRK4:
-      return f64 ? env_shape_t<SysL3RK4<double>, double>(which, a, o) : env_shape_t<SysL3RK4<float>, float>(which, a, o);
-    case LZ_SYS_LORENZ4 + kSysRK4:
-      return f64 ? env_shape_t<SysL4RK4<double>, double>(which, a, o) : env_shape_t<SysL4RK4<float>, float>(which, a, o);
-    case LZ_SYS_PMSM: return env_shape_t<SysPMSM, float>(which, a, o);
-    case LZ_SYS_HR: return f64 ? env_shape_t<SysHR<double>, double>(which, a, o) : env_shape_t<SysHR<float>, float>(which, a, o);
-    case LZ_SYS_T1: return f64 ? env_shape_t<SysT1<double>, double>(which, a, o) : env_shape_t<SysT1<float>, float>(which, a, o);
-    case LZ_SYS_T2: return f64 ? env_shape_t<SysT2<double>, double>(which, a, o) : env_shape_t<SysT2<float>, float>(which, a, o);
-    case LZ_SYS_TP: return f64 ? env_shape_t<SysTP<double>, double>(which, a, o) : env_shape_t<SysTP<float>, float>(which, a, o);
-    case LZ_SYS_SC: return f64 ? env_shape_t<SysSC<double>, double>(which, a, o) : env_shape_t<SysSC<float>, float>(which, a, o);
-  }
-  return (int)hipErrorInvalidValue;
+int env_launch_shape(EnvLaunch which, int system, int f64, const KArgs& a, EnvShape& o) {
+  return for_system(system, f64 != 0, [&](auto tag) {
+    return env_shape_t<typename decltype(tag)::Sys, typename decltype(tag)::T>(which, a, o);
+  });
+}
+
+// ------------------------------------------------------------------ system facts
+const SysInfo& sys_info(int system) {
+  struct Table {
+    SysInfo row[LZ_SYS_SC + 2];  // the last one stays zero: an unknown system
+    Table() : row{} {
+      for (int s = 0; s <= LZ_SYS_SC; ++s)
+        for_system(s, false, [&](auto tag) { return row[s] = sys_info_of<decltype(tag)>(), 0; });
+    }
+  };
+  static const Table t;
+  return t.row[system >= 0 && system <= LZ_SYS_SC ? system : LZ_SYS_SC + 1];
 }
 
 // ------------------------------------------------------------------ resident step server
@@ -1807,39 +1782,19 @@ static int launch_vn(const KArgs& a, const VArgs& v, hipStream_t s) {
 
 int launch_step_vecnorm(int system, int f64, const KArgs& a, const VArgs& v, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (system) {
-    case LZ_SYS_LORENZ3:
-      return f64 ? launch_vn<SysL3<double>, double>(a, v, s) : launch_vn<SysL3<float>, float>(a, v, s);
-    case LZ_SYS_LORENZ4:
-      return f64 ? launch_vn<SysL4<double>, double>(a, v, s) : launch_vn<SysL4<float>, float>(a, v, s);
-    case LZ_SYS_LORENZ3 + kSysRK4:
-      return f64 ? launch_vn<SysL3RK4<double>, double>(a, v, s) : launch_vn<SysL3RK4<float>, float>(a, v, s);
-    case LZ_SYS_LORENZ4 + kSysRK4:
-      return f64 ? launch_vn<SysL4RK4<double>, double>(a, v, s) : launch_vn<SysL4RK4<float>, float>(a, v, s);
-    case LZ_SYS_PMSM:
-      return launch_vn<SysPMSM, float>(a, v, s);
-    case LZ_SYS_HR:
-      return f64 ? launch_vn<SysHR<double>, double>(a, v, s) : launch_vn<SysHR<float>, float>(a, v, s);
-    case LZ_SYS_T1:
-      return f64 ? launch_vn<SysT1<double>, double>(a, v, s) : launch_vn<SysT1<float>, float>(a, v, s);
-    case LZ_SYS_T2:
-      return f64 ? launch_vn<SysT2<double>, double>(a, v, s) : launch_vn<SysT2<float>, float>(a, v, s);
-    case LZ_SYS_TP:
-      return f64 ? launch_vn<SysTP<double>, double>(a, v, s) : launch_vn<SysTP<float>, float>(a, v, s);
-    case LZ_SYS_SC:
-      return f64 ? launch_vn<SysSC<double>, double>(a, v, s) : launch_vn<SysSC<float>, float>(a, v, s);
-  }
-  return (int)hipErrorInvalidValue;
+  return for_system(system, f64 != 0, [&](auto tag) {
+    return launch_vn<typename decltype(tag)::Sys, typename decltype(tag)::T>(a, v, s);
+  });
 }
 
 int launch_reset(int system, int f64, const KArgs& a, void* stream) {
-  return dispatch(0, system, f64, a, stream);
+  return dispatch(EnvLaunch::Reset, system, f64, a, stream);
 }
 int launch_step(int system, int f64, const KArgs& a, void* stream) {
-  return dispatch(1, system, f64, a, stream);
+  return dispatch(EnvLaunch::Step, system, f64, a, stream);
 }
 int launch_rollout(int system, int f64, const KArgs& a, void* stream) {
-  return dispatch(2, system, f64, a, stream);
+  return dispatch(EnvLaunch::Rollout, system, f64, a, stream);
 }
 
 // Indexed plane access (lz_get_state / lz_set_state with indices): one lane per index,

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "lz_body.h"
+#include "lz_dispatch.h"
 #include "lz_internal.h"
 #include "lz_philox.h"
 #include "lz_systems.h"
@@ -2665,22 +2666,6 @@ PolShape f32_policy_shape(int64_t n, int num_cus, int variant) {
   return s;
 }
 
-int launch_rollout_policy_f32(int system, const KArgs& a, const PArgs& p, const PolShape& grid,
-                              void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (system) {
-    case LZ_SYS_LORENZ3: return launch_pol_f32<SysL3<float>, true>(a, p, grid, s);
-    case LZ_SYS_LORENZ4: return launch_pol_f32<SysL4<float>, true>(a, p, grid, s);
-    case LZ_SYS_PMSM: return launch_pol_f32<SysPMSM, true>(a, p, grid, s);
-    case LZ_SYS_HR: return launch_pol_f32<SysHR<float>, true>(a, p, grid, s);
-    case LZ_SYS_T1: return launch_pol_f32<SysT1<float>>(a, p, grid, s);
-    case LZ_SYS_T2: return launch_pol_f32<SysT2<float>>(a, p, grid, s);
-    case LZ_SYS_TP: return launch_pol_f32<SysTP<float>>(a, p, grid, s);
-    case LZ_SYS_SC: return launch_pol_f32<SysSC<float>>(a, p, grid, s);
-  }
-  return (int)hipErrorInvalidValue;
-}
-
 template <class Sys>
 static int launch_step_f32(const KArgs& a, const PArgs& p, const PStepArgs& st, const PolShape& sh,
                            hipStream_t s) {
@@ -2691,57 +2676,24 @@ static int launch_step_f32(const KArgs& a, const PArgs& p, const PStepArgs& st, 
   return (int)hipGetLastError();
 }
 
-int launch_policy_step_f32(int system, const KArgs& a, const PArgs& p, const PStepArgs& st,
-                           const PolShape& grid, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (system) {
-    case LZ_SYS_LORENZ3: return launch_step_f32<SysL3<float>>(a, p, st, grid, s);
-    case LZ_SYS_LORENZ4: return launch_step_f32<SysL4<float>>(a, p, st, grid, s);
-    case LZ_SYS_PMSM: return launch_step_f32<SysPMSM>(a, p, st, grid, s);
-    case LZ_SYS_HR: return launch_step_f32<SysHR<float>>(a, p, st, grid, s);
-    case LZ_SYS_T1: return launch_step_f32<SysT1<float>>(a, p, st, grid, s);
-    case LZ_SYS_T2: return launch_step_f32<SysT2<float>>(a, p, st, grid, s);
-    case LZ_SYS_TP: return launch_step_f32<SysTP<float>>(a, p, st, grid, s);
-    case LZ_SYS_SC: return launch_step_f32<SysSC<float>>(a, p, st, grid, s);
-  }
-  return (int)hipErrorInvalidValue;
-}
-
-int launch_rollout_policy(int system, const KArgs& a, const PArgs& p, const PolShape& grid,
-                          void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (system) {
-    case LZ_SYS_LORENZ3: return launch_pol<SysL3<float>>(a, p, grid, s);
-    case LZ_SYS_LORENZ4: return launch_pol<SysL4<float>>(a, p, grid, s);
-    case LZ_SYS_PMSM: return launch_pol<SysPMSM>(a, p, grid, s);
-    case LZ_SYS_HR: return launch_pol<SysHR<float>>(a, p, grid, s);
-    case LZ_SYS_T1: return launch_pol<SysT1<float>>(a, p, grid, s);
-    case LZ_SYS_T2: return launch_pol<SysT2<float>>(a, p, grid, s);
-    case LZ_SYS_TP: return launch_pol<SysTP<float>>(a, p, grid, s);
-    case LZ_SYS_SC: return launch_pol<SysSC<float>>(a, p, grid, s);
-  }
-  return (int)hipErrorInvalidValue;
-}
-
 // waves of 16 envs, one workgroup per CU (the LDS holds one): 8 (two per SIMD, 256
 // registers) for both extractors -- the LayerNorm variant ran 4 (one per SIMD, 512
 // registers) until its frame stack was distributed over the lane groups; then 8 waves
 // measured 5.96e8 vs 4.50e8 env-steps/s at HR 32,768 x 2048 (profiles/r03/attn_f32) with
 // 20 spilled VGPRs; LZ_ATTN_F32_WAVES=4|8 forces
-PolShape attn_f32_policy_shape(int64_t n, int num_cus, int ln) {
+PolShape attn_f32_policy_shape(int64_t n, int num_cus, int) {
   static const int forced = [] {
     const char* e = std::getenv("LZ_ATTN_F32_WAVES");
     const int w = e ? std::atoi(e) : 0;
     return w == 4 || w == 8 ? w : 0;
   }();
-  (void)ln;
   PolShape s = {16, forced ? forced : 8, 0, 0};
   const int64_t groups = ((n + 15) / 16 + s.waves - 1) / s.waves;
   s.grid = (int)(groups < num_cus ? groups : num_cus);
   return s;
 }
 
-PolShape attn_policy_shape(int64_t n, int num_cus) {
+PolShape attn_policy_shape(int64_t n, int num_cus, int) {
   PolShape s = {32, 4, 3, 0};
   const int64_t groups = ((n + 31) / 32 + 3) / 4;
   s.grid = (int)(groups < num_cus ? groups : num_cus);
@@ -2753,22 +2705,6 @@ static int launch_pol_attn(const KArgs& a, const PArgs& p, const PolShape& sh, h
   hipLaunchKernelGGL((k_rollout_policy<Sys, 4, 32, kAttn>), dim3((unsigned)sh.grid), dim3(4 * 64), 0, s,
                      a, p);
   return (int)hipGetLastError();
-}
-
-int launch_rollout_policy_attn(int system, const KArgs& a, const PArgs& p, const PolShape& grid,
-                               void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (system) {
-    case LZ_SYS_LORENZ3: return launch_pol_attn<SysL3<float>>(a, p, grid, s);
-    case LZ_SYS_LORENZ4: return launch_pol_attn<SysL4<float>>(a, p, grid, s);
-    case LZ_SYS_PMSM: return launch_pol_attn<SysPMSM>(a, p, grid, s);
-    case LZ_SYS_HR: return launch_pol_attn<SysHR<float>>(a, p, grid, s);
-    case LZ_SYS_T1: return launch_pol_attn<SysT1<float>>(a, p, grid, s);
-    case LZ_SYS_T2: return launch_pol_attn<SysT2<float>>(a, p, grid, s);
-    case LZ_SYS_TP: return launch_pol_attn<SysTP<float>>(a, p, grid, s);
-    case LZ_SYS_SC: return launch_pol_attn<SysSC<float>>(a, p, grid, s);
-  }
-  return (int)hipErrorInvalidValue;
 }
 
 template <class Sys>
@@ -2800,26 +2736,43 @@ static int launch_pol_attn_f32(int ln, int n_stack, const KArgs& a, const PArgs&
   return (int)hipGetLastError();
 }
 
-int launch_rollout_policy_attn_f32(int system, int ln, int n_stack, const KArgs& a, const PArgs& p,
-                                   const PolShape& grid, void* stream) {
+// One entry for every policy rollout: the system picks the Sys type, the kind the
+// launcher; a kind the system list (lz_dispatch.h) does not name for the system is not
+// instantiated for it and refused here (lz_api.cpp refuses it first, with a message).
+int launch_policy(PolicyKind kind, int system, int n_stack, const KArgs& a, const PArgs& p,
+                  const PStepArgs* st, const PolShape& sh, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (system) {  // code/train.py's learner is HR; lorenz_filter's is HR on VecFrameStack(4)
-    case LZ_SYS_LORENZ3: return launch_pol_attn_f32<SysL3<float>>(ln, n_stack, a, p, grid, s);
-    case LZ_SYS_PMSM: return launch_pol_attn_f32<SysPMSM>(ln, n_stack, a, p, grid, s);
-    case LZ_SYS_HR: return launch_pol_attn_f32<SysHR<float>>(ln, n_stack, a, p, grid, s);
-  }
-  return (int)hipErrorInvalidValue;
-}
-
-int launch_rollout_policy_attn_ln(int system, int n_stack, const KArgs& a, const PArgs& p,
-                                  const PolShape& grid, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (system) {  // the reference's frame-stacked learner is HR (lorenz_filter/train.py)
-    case LZ_SYS_LORENZ3: return launch_pol_attn_ln<SysL3<float>>(n_stack, a, p, grid, s);
-    case LZ_SYS_PMSM: return launch_pol_attn_ln<SysPMSM>(n_stack, a, p, grid, s);
-    case LZ_SYS_HR: return launch_pol_attn_ln<SysHR<float>>(n_stack, a, p, grid, s);
-  }
-  return (int)hipErrorInvalidValue;
+  return for_system(system, false, [&](auto tag) -> int {
+    using Tag = decltype(tag);
+    using Sys = typename Tag::Sys;
+    switch (kind) {
+      case PolicyKind::Bf16Mlp:
+        if constexpr (Tag::runs(PolicyKind::Bf16Mlp)) return launch_pol<Sys>(a, p, sh, s);
+        break;
+      case PolicyKind::Bf16Attn:
+        if constexpr (Tag::runs(PolicyKind::Bf16Attn)) return launch_pol_attn<Sys>(a, p, sh, s);
+        break;
+      case PolicyKind::Bf16AttnLn:
+        if constexpr (Tag::runs(PolicyKind::Bf16AttnLn)) return launch_pol_attn_ln<Sys>(n_stack, a, p, sh, s);
+        break;
+      case PolicyKind::F32Mlp:
+        if constexpr (Tag::runs(PolicyKind::F32Mlp))
+          return launch_pol_f32<Sys, (Tag::policies & kPolMlpI8) != 0>(a, p, sh, s);
+        break;
+      case PolicyKind::F32Attn:
+        if constexpr (Tag::runs(PolicyKind::F32Attn)) return launch_pol_attn_f32<Sys>(0, n_stack, a, p, sh, s);
+        break;
+      case PolicyKind::F32AttnLn:
+        if constexpr (Tag::runs(PolicyKind::F32AttnLn)) return launch_pol_attn_f32<Sys>(1, n_stack, a, p, sh, s);
+        break;
+      case PolicyKind::F32MlpStep:
+        if constexpr (Tag::runs(PolicyKind::F32MlpStep)) {
+          if (st) return launch_step_f32<Sys>(a, p, *st, sh, s);
+        }
+        break;
+    }
+    return (int)hipErrorInvalidValue;
+  });
 }
 
 int launch_policy_moments_final(const double* partials, int nparts, int width, double count,

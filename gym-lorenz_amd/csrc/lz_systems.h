@@ -108,6 +108,8 @@ struct SysL3 {
   static constexpr bool kUsesAction = true, kNoise = false;
   static constexpr bool kNeverTerminates = true;  // step() returns false: :85-89
   static constexpr int kStepPlane = LZ_L3_STEP;
+  static constexpr int state_dim = 3, n_planes = 4, t_planes = 3;  // t_planes: leading planes of T
+  static_assert(n_planes == LZ_L3_STEP + 1 && state_dim == LZ_L3_STEP, "lorenz_env.h LORENZ3 planes");
   T x, y, z;
   T sg, rh, be, dt, cl;
 
@@ -166,6 +168,8 @@ struct SysL4 {
   static constexpr int A = 3, O = 8, NI = 8;
   static constexpr bool kUsesAction = false, kNoise = false;
   static constexpr int kStepPlane = LZ_L4_STEP;
+  static constexpr int state_dim = 8, n_planes = 9, t_planes = 8;
+  static_assert(n_planes == LZ_L4_STEP + 1 && state_dim == LZ_L4_STEP, "lorenz_env.h LORENZ4 planes");
   T m[4], s[4];
   T pa, pb, pc, dt;
 
@@ -319,6 +323,9 @@ struct SysPMSM {
   static constexpr int A = 2, O = 6, NI = 6;
   static constexpr bool kUsesAction = true, kNoise = true;
   static constexpr int kStepPlane = LZ_PMSM_STEP;
+  static constexpr int state_dim = 6, n_planes = 11, t_planes = 9;  // adam_step, step: int32
+  static_assert(n_planes == LZ_PMSM_STEP + 1 && state_dim == LZ_PMSM_LAMBDA && t_planes == LZ_PMSM_ADAM_STEP,
+                "lorenz_env.h PMSM planes");
   float s1[3], s2[3], lam, mt, vt;
   int32_t adam;
   float sg, gm, dt, fmax, lr, b1, b2, eps, thr, tterm, c1, c2, alpha;
@@ -608,6 +615,9 @@ struct SysHR {
   static constexpr int A = 2, O = 6, NI = 7;
   static constexpr bool kUsesAction = true, kNoise = true;
   static constexpr int kStepPlane = LZ_HR_STEP;
+  static constexpr int state_dim = 6, n_planes = 10, t_planes = 7;  // filtered_action is float32
+  static_assert(n_planes == LZ_HR_STEP + 1 && state_dim == LZ_HR_SIGMA && t_planes == LZ_HR_FA,
+                "lorenz_env.h HR planes");
 #ifndef LZ_HR_PACKED
 #define LZ_HR_PACKED 1
 #endif
@@ -822,6 +832,8 @@ struct SysT1 {
   static constexpr int A = 2, O = 6, NI = 3;
   static constexpr bool kUsesAction = true, kNoise = false;
   static constexpr int kStepPlane = LZ_T1_STEP;
+  static constexpr int state_dim = 3, n_planes = 4, t_planes = 3;
+  static_assert(n_planes == LZ_T1_STEP + 1 && state_dim == LZ_T1_STEP, "lorenz_env.h T1 planes");
   T v[3];
   T pa, pb, dt;
   float cl;
@@ -873,6 +885,8 @@ struct SysT2 {
   static constexpr int A = 3, O = 8, NI = 8;
   static constexpr bool kUsesAction = true, kNoise = false;
   static constexpr int kStepPlane = LZ_T2_STEP;
+  static constexpr int state_dim = 8, n_planes = 9, t_planes = 8;
+  static_assert(n_planes == LZ_T2_STEP + 1 && state_dim == LZ_T2_STEP, "lorenz_env.h T2 planes");
   T m[4], s[4];
   T pa, pb, pc, dt, pd, ph, dmp;
   float cl, gain;
@@ -948,6 +962,8 @@ struct SysTP {
   static constexpr int A = 2, O = 6, NI = 6;
   static constexpr bool kUsesAction = true, kNoise = true;
   static constexpr int kStepPlane = LZ_TP_STEP;
+  static constexpr int state_dim = 6, n_planes = 7, t_planes = 6;
+  static_assert(n_planes == LZ_TP_STEP + 1 && state_dim == LZ_TP_STEP, "lorenz_env.h TP planes");
   T m[3], s[3];
   T pa, pb, dt;
   float cl, gain;
@@ -1020,6 +1036,8 @@ struct SysSC {
   static constexpr int A = 2, O = 6, NI = 3;
   static constexpr bool kUsesAction = false, kNoise = true;
   static constexpr int kStepPlane = LZ_SC_STEP;
+  static constexpr int state_dim = 3, n_planes = 4, t_planes = 3;
+  static_assert(n_planes == LZ_SC_STEP + 1 && state_dim == LZ_SC_STEP, "lorenz_env.h SC planes");
   T v[3];
   T pa, pb, dt;
   double nstd;

@@ -105,3 +105,64 @@ def test_legacy_rollout_equals_steps(gl, key, n):
         assert bits_equal(_np(r), _np(rew[k])), k
         assert np.array_equal(_np(d), _np(done[k])), k
     assert (_np(done) & 2).any()  # TimeLimit truncation + auto-reset exercised
+
+
+# lz_get_info per (system, dtype, add_noise, add_filter, max_episode_steps): state_dim,
+# action_dim, obs_dim, init_dim, n_planes, state_io_bytes, bytes_per_env_step -- recorded
+# from the library before the dims moved onto the Sys types (lz_dispatch.h sys_info_of);
+# max_episode_steps > 0 makes the handle count steps (the step plane joins the traffic)
+INFO_FIELDS = ("state_dim", "action_dim", "obs_dim", "init_dim", "n_planes", "state_io_bytes",
+               "bytes_per_env_step")
+INFO = [
+    ('lorenz3',       'float32', None,  False, 0, (3, 3, 6, 3, 4, 24, 65)),
+    ('lorenz3',       'float32', None,  False, 7, (3, 3, 6, 3, 4, 32, 73)),
+    ('lorenz3',       'float64', None,  False, 0, (3, 3, 6, 3, 4, 48, 117)),
+    ('lorenz3',       'float64', None,  False, 7, (3, 3, 6, 3, 4, 56, 125)),
+    ('lorenz4',       'float32', None,  False, 0, (8, 3, 8, 8, 9, 64, 101)),
+    ('lorenz4',       'float32', None,  False, 7, (8, 3, 8, 8, 9, 72, 109)),
+    ('lorenz4',       'float64', None,  False, 0, (8, 3, 8, 8, 9, 128, 201)),
+    ('lorenz4',       'float64', None,  False, 7, (8, 3, 8, 8, 9, 136, 209)),
+    ('pmsm',          'float32', None,  False, 0, (6, 2, 6, 6, 11, 88, 125)),
+    ('pmsm',          'float32', None,  False, 7, (6, 2, 6, 6, 11, 88, 125)),
+    ('hr',            'float32', False, False, 0, (6, 2, 6, 7, 10, 48, 85)),
+    ('hr',            'float32', False, False, 7, (6, 2, 6, 7, 10, 56, 93)),
+    ('hr',            'float32', False, True,  0, (6, 2, 6, 7, 10, 64, 101)),
+    ('hr',            'float32', False, True,  7, (6, 2, 6, 7, 10, 72, 109)),
+    ('hr',            'float32', True,  False, 0, (6, 2, 6, 7, 10, 52, 89)),
+    ('hr',            'float32', True,  False, 7, (6, 2, 6, 7, 10, 60, 97)),
+    ('hr',            'float32', True,  True,  0, (6, 2, 6, 7, 10, 68, 105)),
+    ('hr',            'float32', True,  True,  7, (6, 2, 6, 7, 10, 76, 113)),
+    ('hr',            'float64', False, False, 0, (6, 2, 6, 7, 10, 96, 161)),
+    ('hr',            'float64', False, False, 7, (6, 2, 6, 7, 10, 104, 169)),
+    ('hr',            'float64', False, True,  0, (6, 2, 6, 7, 10, 112, 177)),
+    ('hr',            'float64', False, True,  7, (6, 2, 6, 7, 10, 120, 185)),
+    ('hr',            'float64', True,  False, 0, (6, 2, 6, 7, 10, 104, 169)),
+    ('hr',            'float64', True,  False, 7, (6, 2, 6, 7, 10, 112, 177)),
+    ('hr',            'float64', True,  True,  0, (6, 2, 6, 7, 10, 120, 185)),
+    ('hr',            'float64', True,  True,  7, (6, 2, 6, 7, 10, 128, 193)),
+    ('transient1',    'float32', None,  False, 0, (3, 2, 6, 3, 4, 24, 61)),
+    ('transient1',    'float32', None,  False, 7, (3, 2, 6, 3, 4, 32, 69)),
+    ('transient1',    'float64', None,  False, 0, (3, 2, 6, 3, 4, 48, 113)),
+    ('transient1',    'float64', None,  False, 7, (3, 2, 6, 3, 4, 56, 121)),
+    ('transient2',    'float32', None,  False, 0, (8, 3, 8, 8, 9, 64, 113)),
+    ('transient2',    'float32', None,  False, 7, (8, 3, 8, 8, 9, 72, 121)),
+    ('transient2',    'float64', None,  False, 0, (8, 3, 8, 8, 9, 128, 213)),
+    ('transient2',    'float64', None,  False, 7, (8, 3, 8, 8, 9, 136, 221)),
+    ('transient_pmsm', 'float32', None,  False, 0, (6, 2, 6, 6, 7, 48, 85)),
+    ('transient_pmsm', 'float32', None,  False, 7, (6, 2, 6, 6, 7, 56, 93)),
+    ('transient_pmsm', 'float64', None,  False, 0, (6, 2, 6, 6, 7, 96, 161)),
+    ('transient_pmsm', 'float64', None,  False, 7, (6, 2, 6, 6, 7, 104, 169)),
+    ('singlecontrol', 'float32', None,  False, 0, (3, 2, 6, 3, 4, 24, 53)),
+    ('singlecontrol', 'float32', None,  False, 7, (3, 2, 6, 3, 4, 32, 61)),
+    ('singlecontrol', 'float64', None,  False, 0, (3, 2, 6, 3, 4, 48, 105)),
+    ('singlecontrol', 'float64', None,  False, 7, (3, 2, 6, 3, 4, 56, 113)),
+]
+
+
+@pytest.mark.parametrize("system,dtype,add_noise,add_filter,mes,want", INFO)
+def test_get_info_recorded(gl, system, dtype, add_noise, add_filter, mes, want):
+    be = gl.BatchedEnv(system, 64, dtype=dtype, add_noise=add_noise, add_filter=add_filter,
+                       max_episode_steps=mes)
+    got = tuple(int(getattr(be.info, f)) for f in INFO_FIELDS)
+    assert got == want
+    be.close()

@@ -103,6 +103,23 @@ CASES = [
     (F32_LN, "hr", 1000, 4, 0, 4, "policy_attn_f32", False),
     (F32_LN, "hr", 33001, 3, 0, 4, "policy_attn_f32", True),       # 258 groups, ragged
 ]
+# Every (family, system) arm the library builds runs at least once: the systems the rows
+# above leave out, at a small ragged size (a mis-wired arm steps another system's env).
+CASES += [(kind, system, 333, 4, 0, 1, kernel, False) for kind, kernel, systems in (
+    (F32_MLP, "policy_split", ("transient1", "transient2", "transient_pmsm", "singlecontrol")),
+    (F32_STEP, "policy_step", ("lorenz3", "hr", "transient1", "transient2", "transient_pmsm",
+                               "singlecontrol")),
+    (BF16_MLP, "policy_pair_pipe", ("transient1",)),
+    (BF16_ATTN, "policy_attn", ("lorenz4", "transient1", "transient2", "transient_pmsm",
+                                "singlecontrol")),
+) for system in systems]
+CASES += [  # the LORENZ3 / PMSM arms of the kinds built for LORENZ3 / PMSM / HR only
+    (BF16_LN, "lorenz3", 333, 4, 0, 4, "policy_attn", False),
+    (BF16_LN, "pmsm", 333, 4, 0, 4, "policy_attn", False),
+    (F32_ATTN, "lorenz3", 333, 4, 0, 1, "policy_attn_f32", False),
+    (F32_LN, "lorenz3", 333, 4, 0, 4, "policy_attn_f32", False),
+    (F32_LN, "pmsm", 333, 4, 0, 4, "policy_attn_f32", False),
+]
 CALL = {F32_MLP: 3, F32_STEP: 4, BF16_MLP: 2, BF16_ATTN: 5, BF16_LN: 6, F32_ATTN: 7, F32_LN: 8}
 
 

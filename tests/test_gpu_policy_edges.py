@@ -110,6 +110,60 @@ def test_errors(pol):
     del c
 
 
+STACKED_MSG = "the frame-stacked rollout runs LORENZ3 / PMSM / HR"
+
+
+@pytest.mark.parametrize("system", ["lorenz4", "transient1"])
+@pytest.mark.parametrize("entry,stacked,msg", [
+    ("lz_rollout_policy_attn_f32", False, "the float32 attention rollout runs LORENZ3 / PMSM / HR"),
+    ("lz_rollout_policy_attn_stack", True, STACKED_MSG),
+    ("lz_rollout_policy_attn_stack_f32", True, STACKED_MSG),
+])
+def test_family_refused_for_unbuilt_system(system, entry, stacked, msg):
+    """The float32 attention and both frame-stacked rollouts are built for LORENZ3 / PMSM /
+    HR: any other system is LZ_ERR_UNSUPPORTED, decided before any buffer is looked at."""
+    import gym_lorenz as gl
+    from gym_lorenz import _native as nat
+
+    env = gl.BatchedEnv(system, 77)
+    env.reset()
+    r = nat.LzPolicyRolloutArgs()
+    r.K = 2
+    args = [env._h, ctypes.byref(r)]
+    if stacked:
+        buf = torch.zeros(77 * 4 * env.obs_dim, device=env.device)
+        args += [4, ctypes.c_void_p(buf.data_ptr()), ctypes.c_void_p(buf.data_ptr())]
+    assert getattr(nat.lib, entry)(*args) == nat.LZ_ERR_UNSUPPORTED
+    assert nat.lib.lz_last_error().decode() == msg
+    env.close()
+
+
+@pytest.mark.parametrize("entry,system,flags_ok", [
+    ("lz_rollout_policy", "pmsm", False),        # bf16 MlpPolicy
+    ("lz_rollout_policy_attn", "hr", False),     # bf16 attention
+    ("lz_rollout_policy_f32", "transient1", False),  # float32 MlpPolicy: no i8x4 for the legacy systems
+    ("lz_rollout_policy_f32", "lorenz4", True),  # ... but for LORENZ4 (refused later: NULL buffers)
+])
+def test_i8x4_flag_refusals(entry, system, flags_ok):
+    import gym_lorenz as gl
+    from gym_lorenz import _native as nat
+
+    env = gl.BatchedEnv(system, 77)
+    env.reset()
+    r = nat.LzPolicyRolloutArgs()
+    r.K = 2
+    r.flags = nat.POLICY_I8X4
+    st = getattr(nat.lib, entry)(env._h, ctypes.byref(r))
+    err = nat.lib.lz_last_error().decode()
+    if flags_ok:
+        assert st == nat.LZ_ERR_INVALID and err == "blob / obs / rollout buffers must be non-NULL"
+    else:
+        assert st == nat.LZ_ERR_UNSUPPORTED
+        assert err == ("the i8x4 MlpPolicy rollout runs LORENZ3 / LORENZ4 / PMSM / HR" if entry.endswith("f32")
+                       else "LZ_POLICY_I8X4 runs the float32 (attention / MlpPolicy) rollouts only")
+    env.close()
+
+
 # lz_episode_starts: SB3's episode_starts buffer of one collect from the done codes,
 # exact vs the torch expression it replaced; grid-stride beyond 2,097,152 elements
 @pytest.mark.parametrize("n,K", [(1, 1), (5, 1), (300, 7), (4099, 16), (200003, 16)])

@@ -196,3 +196,25 @@ def test_rk4_vecnorm_step_and_policy_rejection(gl, orc):
         col = FusedRolloutCollector(be, sd, precision="fp32", vecnorm_update="rollout")
         col.reset()
         col.collect(2)
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_rk4_vecnorm_step_lorenz4(gl, dtype):
+    """The LORENZ4 RK4 arm of lz_step_vecnorm: its raw outputs are lz_step's, bit for bit
+    (LORENZ4 reads no action; the VecEnv view of a float64 env is float32)."""
+    from gym_lorenz.vec_env import LorenzVecEnv
+    from gym_lorenz.vec_normalize import LorenzVecNormalize
+
+    n = 300
+    venv = LorenzVecNormalize(LorenzVecEnv("lorenz_transient-v0", n, seed=5, return_tensors=True,
+                                           dtype=dtype, integrator="rk4"),
+                              norm_obs=True, norm_reward=False)
+    be = gl.BatchedEnv("lorenz4", n, seed=5, dtype=dtype, integrator="rk4")
+    venv.reset()
+    be.reset()
+    a = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+    for _ in range(5):
+        venv.step(a)
+        o, r, d = be.step(a)
+    assert bits_equal(_np(venv.get_original_obs()), _np(o).astype(np.float32))
+    be.close()
