@@ -1151,6 +1151,14 @@ const PolicyRow kPolicyTable[] = {  // indexed by PolicyKind
      lz::attn_f32_policy_shape, true, true, "the frame-stacked rollout runs LORENZ3 / PMSM / HR"},
     {lz::PolicyKind::F32MlpStep, LZ_CALL_POLICY_STEP_F32, LZ_KERNEL_POLICY_STEP, lz::f32_policy_shape, false,
      false, ""},
+    {lz::PolicyKind::EvalF32Mlp, LZ_CALL_EVALUATE_POLICY_F32, LZ_KERNEL_EVAL, lz::eval_f32_policy_shape, false,
+     false, "the fused MlpPolicy evaluation runs LORENZ3 / LORENZ4 / PMSM / HR"},
+    {lz::PolicyKind::EvalF32Attn, LZ_CALL_EVALUATE_POLICY_ATTN_F32, LZ_KERNEL_EVAL_ATTN_F32,
+     lz::eval_attn_f32_policy_shape, false, false,
+     "the fused attention evaluation runs LORENZ3 / PMSM / HR"},
+    {lz::PolicyKind::EvalF32AttnLn, LZ_CALL_EVALUATE_POLICY_ATTN_STACK_F32, LZ_KERNEL_EVAL_ATTN_F32,
+     lz::eval_attn_f32_policy_shape, true, false,
+     "the fused frame-stacked evaluation runs LORENZ3 / PMSM / HR"},
 };
 static const PolicyRow& policy_row(lz::PolicyKind k) { return kPolicyTable[(int)k]; }
 static lz::PolShape policy_shape_of(const lz_handle* h, const PolicyRow& row) {
@@ -1382,6 +1390,77 @@ lz_status lz_rollout_policy_attn_f32(lz_handle* h, const lz_policy_rollout_args*
 lz_status lz_rollout_policy_attn_stack_f32(lz_handle* h, const lz_policy_rollout_args* r,
                                            int32_t n_stack, const float* stack_in, float* stack_out) {
   return rollout_policy(h, r, lz::PolicyKind::F32AttnLn, n_stack, stack_in, stack_out);
+}
+
+// ---- fused policy evaluation (lorenz_env.h LZ_EVAL_*; lz_internal.h EArgs)
+static lz_status evaluate_policy(lz_handle* h, const lz_policy_eval_args* e, lz::PolicyKind kind,
+                                 int n_stack = 1, const float* stack_in = nullptr,
+                                 float* stack_out = nullptr) {
+  if (!h || !e) return fail(LZ_ERR_INVALID, "handle/args is NULL");
+  RESIDENT_QUIESCE(h);
+  const PolicyRow& row = policy_row(kind);
+  if (e->flags & LZ_POLICY_BOOTSTRAP)
+    return fail(LZ_ERR_INVALID, "an evaluation reports the env's own rewards: no LZ_POLICY_BOOTSTRAP");
+  if (e->flags & LZ_POLICY_I8X4)
+    return fail(LZ_ERR_UNSUPPORTED, "the fused evaluation runs the float32 policies only, not LZ_POLICY_I8X4");
+  if (h->f64) return fail(LZ_ERR_UNSUPPORTED, "the fused evaluation runs float32 handles only");
+  if (sys_key(h) != h->cfg.system)
+    return fail(LZ_ERR_UNSUPPORTED, "the fused evaluation runs the reference's Euler integrator only");
+  if (!(h->desc->policies & lz::pol_bit(kind))) return fail(LZ_ERR_UNSUPPORTED, "%s", row.refusal);
+  if (row.stacked) {
+    if (n_stack != 1 && n_stack != 4) return fail(LZ_ERR_UNSUPPORTED, "n_stack must be 1 or 4");
+    if (n_stack * h->desc->obs_dim > lz::kLnMaxIn) return fail(LZ_ERR_UNSUPPORTED, "stacked obs > 32 dims");
+    if (e->obs_norm)
+      return fail(LZ_ERR_UNSUPPORTED, "the frame-stacked evaluation takes no VecNormalize statistics");
+    if (!stack_in || !stack_out) return fail(LZ_ERR_INVALID, "stack_in / stack_out must be non-NULL");
+  }
+  if (e->K < 1) return fail(LZ_ERR_INVALID, "K must be >= 1");
+  if (e->skip < 0 || e->max_episodes < 0) return fail(LZ_ERR_INVALID, "skip and max_episodes must be >= 0");
+  if (!e->blob || !e->obs_in || !e->obs_last || !e->stats)
+    return fail(LZ_ERR_INVALID, "blob / obs_in / obs_last / stats must be non-NULL");
+  if (!(e->act_low <= e->act_high)) return fail(LZ_ERR_INVALID, "act_low > act_high");
+  if (!h->was_reset) return fail(LZ_ERR_STATE, "lz_evaluate_policy before the first lz_reset");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const lz::PolShape sh = policy_shape_of(h, row);
+  KArgs a;
+  fill_common(h, a);
+  a.K = e->K;
+  a.tick_adv = (uint64_t)e->K;
+  lz::PArgs p;
+  std::memset(&p, 0, sizeof p);
+  p.blob = static_cast<const uint8_t*>(e->blob);
+  p.obs_in = e->obs_in;
+  p.obs_last = e->obs_last;
+  p.norm = e->obs_norm;
+  p.eps = e->norm_eps;
+  p.clip = e->clip_obs;
+  p.act_lo = e->act_low;
+  p.act_hi = e->act_high;
+  p.pflags = e->flags;
+  p.stack_in = stack_in;
+  p.stack_out = stack_out;
+  lz::EArgs ev;
+  ev.stats = e->stats;
+  ev.skip = e->skip;
+  ev.max_episodes = e->max_episodes;
+  const int err = lz::launch_policy(kind, h->cfg.system, n_stack, a, p, nullptr, sh, h->stream, &ev);
+  if (err != 0) return fail(LZ_ERR_HIP, "policy evaluation launch: %s", hipGetErrorString((hipError_t)err));
+  h->parity ^= 1;
+  ++h->gen;
+  return LZ_OK;
+}
+
+lz_status lz_evaluate_policy_f32(lz_handle* h, const lz_policy_eval_args* e) {
+  return evaluate_policy(h, e, lz::PolicyKind::EvalF32Mlp);
+}
+
+lz_status lz_evaluate_policy_attn_f32(lz_handle* h, const lz_policy_eval_args* e) {
+  return evaluate_policy(h, e, lz::PolicyKind::EvalF32Attn);
+}
+
+lz_status lz_evaluate_policy_attn_stack_f32(lz_handle* h, const lz_policy_eval_args* e, int32_t n_stack,
+                                            const float* stack_in, float* stack_out) {
+  return evaluate_policy(h, e, lz::PolicyKind::EvalF32AttnLn, n_stack, stack_in, stack_out);
 }
 
 lz_status lz_get_launch_shape(const lz_handle* h, int32_t call, lz_launch_shape* out) {

@@ -367,6 +367,17 @@ int launch_vn_apply(int f64, int O, int64_t n, const void* obs, const void* rew,
                     uint8_t* dones, float* term_n, const VnUpdate& upd, const int32_t* counter,
                     int32_t* n_done_out, void* stream);
 
+// Fused policy evaluation (lz_evaluate_policy_*_f32 -> k_evaluate_policy_f32 /
+// k_evaluate_policy_attn_f32): the rollout's loop with the evaluator's per-env float64
+// accumulators (lorenz_env.h LZ_EVAL_*) in registers and one table written at the end.
+// Of PArgs the launch reads blob, obs_in, obs_last, norm, eps, clip, act_lo, act_hi,
+// pflags, stack_in, stack_out.
+struct EArgs {
+  double* stats;         // [LZ_EVAL_COLS][N]
+  int32_t skip;          // first in-episode step index inside the error window
+  int32_t max_episodes;  // 0: every step counts
+};
+
 // The integrator picks the system's instantiation: the launchers' `system` argument is
 // lz_config.system + kSysRK4 for an LZ_INT_RK4 handle of LORENZ3 / LORENZ4 (SysL3RK4 /
 // SysL4RK4, lz_systems.h), else lz_config.system.
@@ -381,6 +392,9 @@ enum class PolicyKind {
   F32Attn,       // lz_rollout_policy_attn_f32
   F32AttnLn,     // lz_rollout_policy_attn_stack_f32
   F32MlpStep,    // lz_policy_step_f32: F32Mlp one step per launch (SB3-exact VecNormalize)
+  EvalF32Mlp,    // lz_evaluate_policy_f32
+  EvalF32Attn,   // lz_evaluate_policy_attn_f32
+  EvalF32AttnLn, // lz_evaluate_policy_attn_stack_f32
 };
 constexpr unsigned pol_bit(PolicyKind k) { return 1u << (int)k; }
 // which kinds are built for a system (lz_dispatch.h for_system): every system runs the
@@ -393,6 +407,11 @@ constexpr unsigned kPolBasic = pol_bit(PolicyKind::Bf16Mlp) | pol_bit(PolicyKind
 constexpr unsigned kPolAll = kPolBasic | pol_bit(PolicyKind::Bf16AttnLn) | pol_bit(PolicyKind::F32Attn) |
                              pol_bit(PolicyKind::F32AttnLn);
 constexpr unsigned kPolMlpI8 = 1u << 16;
+// the fused evaluation: the float32 MlpPolicy for the four systems the reference trains
+// (kPolEval), the two float32 attention actor-critics where their rollouts are built
+// (kPolEvalAttn: LORENZ3 / PMSM / HR)
+constexpr unsigned kPolEval = pol_bit(PolicyKind::EvalF32Mlp);
+constexpr unsigned kPolEvalAttn = pol_bit(PolicyKind::EvalF32Attn) | pol_bit(PolicyKind::EvalF32AttnLn);
 
 // Host-side facts of a system, read off its Sys type (lz_systems.h) through the system
 // list (lz_dispatch.h sys_info_of)
@@ -538,9 +557,13 @@ PolShape attn_f32_policy_shape(int64_t n, int num_cus, int variant);
 // Launch the rollout of `kind` for `system` (lz_config.system: the Euler systems);
 // hipErrorInvalidValue where the kind (or LZ_POLICY_I8X4 in F32Mlp) is not built for the
 // system (SysInfo::policies) or n_stack is not 1 or 4.  n_stack: the *AttnLn kinds';
-// st: F32MlpStep's (PStepArgs above), else nullptr.
+// st: F32MlpStep's (PStepArgs above), else nullptr; ev: the Eval* kinds' (EArgs above).
 int launch_policy(PolicyKind kind, int system, int n_stack, const KArgs& a, const PArgs& p,
-                  const PStepArgs* st, const PolShape& sh, void* stream);
+                  const PStepArgs* st, const PolShape& sh, void* stream, const EArgs* ev = nullptr);
+// the evaluation launches' shapes: f32_policy_shape's wave count with pair = 0 (one wave
+// per 32-env tile: there is no critic to split off) / 16-env waves, 8 per workgroup
+PolShape eval_f32_policy_shape(int64_t n, int num_cus, int variant);
+PolShape eval_attn_f32_policy_shape(int64_t n, int num_cus, int variant);
 int launch_policy_moments_final(const double* partials, int nparts, int width, double count,
                                 double* out, void* stream);
 

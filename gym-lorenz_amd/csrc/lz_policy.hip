@@ -2471,6 +2471,413 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy_attn_f32(KArgs a, PAr
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Fused policy evaluation (lz_evaluate_policy_*_f32; lorenz_env.h LZ_EVAL_*).  What the
+// reference's evaluators do with a trained policy (code/test_evaluate.py:91-150,
+// verify_sync.py:208-237, code/lorenz_filter/test_evaluate.py:94-157, code/lorenz_pmsm/
+// test_evaluate.py:61-166, SB3 evaluate_policy at code/gym_run.py:95): the rollout's loop
+// {normalise, pi net, (sample,) clip, env step} for K steps, with the per-env statistics
+// as float64 running sums in registers next to the env state.  No value net, no
+// bootstrap, no per-step global store: one [LZ_EVAL_COLS][N] table when the K steps are
+// done.  The actions are the rollout kernels' bit for bit (the same mlp_f32 /
+// attn16_extract / attn16_net / step_body calls on the same inputs).
+//
+// The float64 accumulators come in four parts of four: ABS_SUM[4], SQ_SUM[4], MAX_ABS[4]
+// and {RET_SUM, EP_RET_SUM, EP_RET_SQ, ep_ret}.  The MlpPolicy kernel's env-owning lane
+// keeps all four (NP = 4); the attention kernel's four lanes of an env all step it (same
+// bits in each), so lane group G keeps part G alone (NP = 1): four doubles per lane.  The
+// integer counters are cheap and every lane keeps its own.
+struct EvalCount {
+  int32_t t, ep, ep_len, n_win, n_steps, n_ep, ep_len_sum, first_done, n_done_steps;
+  uint32_t done_or;
+};
+
+template <int NP>
+__device__ __forceinline__ void eval_zero(double (*q)[4], EvalCount& c) {
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[p][j] = 0.0;
+  }
+  c.t = c.ep = c.ep_len = c.n_win = c.n_steps = c.n_ep = c.ep_len_sum = c.n_done_steps = 0;
+  c.first_done = -1;
+  c.done_or = 0u;
+}
+
+// One step's bookkeeping: o the observation the step emitted before any auto-reset, r its
+// reward, d its done bits.  part0: the part an NP = 1 lane keeps.
+template <int NP, int ED>
+__device__ __forceinline__ void eval_step(double (*q)[4], EvalCount& c, int part0, const float* o, float r,
+                                          uint8_t d, int k, bool autoreset, int skip, int max_ep) {
+  const bool counted = max_ep == 0 || c.ep < max_ep;
+  const bool win = counted && c.t >= skip;
+  const bool ep_end = d != 0 && autoreset;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int part = NP == 4 ? p : part0;
+    if (part < 3) {
+      if (win) {
+#pragma unroll
+        for (int j = 0; j < ED; ++j) {
+          const double v = (double)fabsf(o[j]);
+          const double m = q[p][j];
+          const double s = part == 0 ? v : v * v;  // the product of two floats: exact
+          q[p][j] = part == 2 ? ((v > m || __builtin_isnan(v)) ? v : m) : m + s;
+        }
+      }
+    } else {
+      if (counted) {
+        q[p][0] += (double)r;  // RET_SUM
+        q[p][3] += (double)r;  // ep_ret
+      }
+      if (ep_end) {
+        if (counted) {
+          const double er = q[p][3];
+          q[p][1] += er;       // EP_RET_SUM
+          q[p][2] += er * er;  // EP_RET_SQ
+        }
+        q[p][3] = 0.0;
+      }
+    }
+  }
+  if (counted) {
+    c.n_steps += 1;
+    c.ep_len += 1;
+  }
+  if (win) c.n_win += 1;
+  c.t += 1;
+  if (d != 0) {
+    c.done_or |= d;
+    c.n_done_steps += 1;
+    if (c.first_done < 0) c.first_done = k;
+    if (autoreset) {
+      if (counted) {
+        c.n_ep += 1;
+        c.ep_len_sum += c.ep_len;
+      }
+      c.ep += 1;
+      c.t = 0;
+      c.ep_len = 0;
+    }
+  }
+}
+
+// The env's columns of the table (plane-major: consecutive envs, coalesced like the state
+// planes).  ints: this lane also writes the counter columns.  bad: the blob's format tag
+// did not match the launch -- the whole table is NaN.
+template <int NP>
+__device__ __forceinline__ void eval_store(double* stats, int64_t n, int64_t i, const double (*q)[4],
+                                           const EvalCount& c, int part0, bool ints, bool bad) {
+  const double qn = __builtin_nan("");
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int part = NP == 4 ? p : part0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int rc = j == 0 ? LZ_EVAL_RET_SUM : j == 1 ? LZ_EVAL_EP_RET_SUM : j == 2 ? LZ_EVAL_EP_RET_SQ
+                                                                            : LZ_EVAL_TAIL_RET;
+      const int col = part < 3 ? 4 * part + j : rc;
+      stats[(int64_t)col * n + i] = bad ? qn : q[p][j];
+    }
+  }
+  if (ints) {
+    const int cols[8] = {LZ_EVAL_N_WIN, LZ_EVAL_N_STEPS, LZ_EVAL_N_EP, LZ_EVAL_EP_LEN_SUM,
+                         LZ_EVAL_TAIL_LEN, LZ_EVAL_FIRST_DONE, LZ_EVAL_DONE_OR, LZ_EVAL_N_DONE_STEPS};
+    const double vals[8] = {(double)c.n_win, (double)c.n_steps, (double)c.n_ep, (double)c.ep_len_sum,
+                            (double)c.ep_len, (double)c.first_done, (double)c.done_or,
+                            (double)c.n_done_steps};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) stats[(int64_t)cols[j] * n + i] = bad ? qn : vals[j];
+  }
+}
+static_assert(LZ_EVAL_SQ_SUM0 == 4 && LZ_EVAL_MAX_ABS0 == 8 && LZ_EVAL_COLS == 24, "table columns");
+
+// The float32 MlpPolicy (kF32* blob): one wave per 32-env tile as k_rollout_policy's
+// kMlpF32 path, the pi net, the Normal constants and the tanh table alone in LDS (75 KB
+// of the blob's 148).
+template <class Sys, int W>
+__global__ __launch_bounds__(W * 64) void k_evaluate_policy_f32(KArgs a, PArgs p, EArgs ev) {
+  constexpr int E = 32;
+  constexpr int O = Sys::O, A = Sys::A, ED = O / 2;
+  constexpr int kCst = 64 + kTanhSegs * 32;
+  static_assert(O <= kPolMaxObs && A <= kPolMaxAct && ED <= 4, "policy tile shape");
+  static_assert(kF32Net % 16 == 0 && kF32LogStd % 16 == 0 && kCst % 16 == 0 && kF32Tag + 16 <= kF32Net,
+                "16-B pieces");
+  __shared__ __attribute__((aligned(64))) uint8_t s_net[kF32Net];
+  __shared__ __attribute__((aligned(16))) uint8_t s_cst[kCst];
+  __shared__ double s_norm[2 * kPolMaxObs];
+  const int tid = (int)threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6, h = lane >> 5;
+  const int slot = lane & 31;
+  const bool owner = h == 0;
+  const bool bad = !blob_is(p.blob, kF32Tag, LZ_BLOB_MLP_F32);
+  blob_to_lds(reinterpret_cast<f4v*>(s_net), reinterpret_cast<const f4v*>(p.blob), kF32Net / 16, tid,
+              W * 64, bad);
+  blob_to_lds(reinterpret_cast<f4v*>(s_cst), reinterpret_cast<const f4v*>(p.blob + kF32LogStd), kCst / 16,
+              tid, W * 64, bad);
+  if (tid < O) {  // VecNormalize: mean and sqrt(var + eps) per obs dim
+    s_norm[tid] = p.norm ? p.norm[tid] : 0.0;
+    s_norm[kPolMaxObs + tid] = p.norm ? sqrt(p.norm[O + tid] + p.eps) : 1.0;
+  }
+  const uint64_t tick = *a.tick_in;
+  if (blockIdx.x == 0 && tid == 0) {
+    *a.counter_next = 0;
+    *a.tick_out = tick + a.tick_adv;
+  }
+  __syncthreads();
+  const float* g_scale = reinterpret_cast<const float*>(s_cst) + 4;
+  const float* ttab = reinterpret_cast<const float*>(s_cst + 64);
+  const bool norm = p.norm != nullptr;
+  const double* mu = s_norm;
+  const double* sd = s_norm + kPolMaxObs;
+  const bool det = (p.pflags & LZ_POLICY_DETERMINISTIC) != 0;
+  const bool autoreset = (a.flags & LZ_FLAG_AUTORESET) != 0;
+  Sys sys;
+  sys.setup(a);
+  const int64_t ntiles = (a.n + E - 1) / E;
+  for (int64_t tile = (int64_t)blockIdx.x * W + wave; tile < ntiles; tile += (int64_t)gridDim.x * W) {
+    const int64_t i = tile * E + slot;
+    const bool live = owner && i < a.n;
+    int32_t steps = 0;
+    bool any_reset = false;
+    double q[4][4];  // this tile's accumulators: zeroed per grid-stride tile
+    EvalCount c;
+    eval_zero<4>(q, c);
+    float o[O];
+#pragma unroll
+    for (int j = 0; j < O; ++j) o[j] = 0.0f;
+    if (live) {
+      sys.load(a, i);
+      if (a.count_steps) steps = static_cast<const int32_t*>(a.pl[Sys::kStepPlane])[i];
+#pragma unroll
+      for (int j = 0; j < O; ++j) o[j] = p.obs_in[i * O + j];
+    }
+    for (int k = 0; k < a.K; ++k) {
+      float x[O];
+      normalize<O>(o, x, norm, mu, sd, p.clip);
+      float mean[A];
+      float xs[(O + 1) / 2];
+      f32_inputs<O, (O + 1) / 2>(x, lane, xs);
+      mlp_f32<(O + 1) / 2, A>(s_net, xs, lane, mean, ttab);
+      float act_c[A];
+      if (live) {
+        float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (!det) {
+          if constexpr (A <= 2) normal2(a.seed, (uint64_t)(a.gid0 + i), tick + (uint64_t)k, z);
+          else normal4(a.seed, (uint64_t)(a.gid0 + i), tick + (uint64_t)k, z);
+        }
+#pragma unroll
+        for (int j = 0; j < A; ++j) {
+          const float aj = det ? mean[j] : mean[j] + z[j] * g_scale[j];  // Normal.rsample
+          act_c[j] = clip(aj, p.act_lo, p.act_hi);
+        }
+      }
+      float on[O], ot[O];
+      float rew = 0.0f;
+      bool did_reset;
+      const uint8_t df = step_body<Sys, float, true, true>(sys, steps, a, i, live, act_c,
+                                                           tick + (uint64_t)k, k, on, rew, did_reset, ot);
+      any_reset = any_reset || did_reset;
+      if (live) eval_step<4, ED>(q, c, 0, ot, rew, df, k, autoreset, ev.skip, ev.max_episodes);
+#pragma unroll
+      for (int j = 0; j < O; ++j) o[j] = on[j];
+    }
+    if (live) {
+#pragma unroll
+      for (int j = 0; j < O; ++j) p.obs_last[i * O + j] = o[j];
+      sys.store(a, i);
+      if (any_reset) sys.store_autoreset_extra(a, i);
+      if (a.count_steps) static_cast<int32_t*>(a.pl[Sys::kStepPlane])[i] = steps;
+      eval_store<4>(ev.stats, a.n, i, q, c, 0, true, bad);
+    }
+  }
+}
+
+// The float32 attention actor-critics (kAF* blob; kLn: the residual + LayerNorm extractor
+// on an S-frame VecFrameStack): 16-env waves as k_rollout_policy_attn_f32.  There is one
+// net to run, so the pi net is DMA'd into the slot once per launch and stays: the step
+// loop has no barrier and no slot swap.  The stack lives distributed over the lane groups
+// and follows the rollout's order exactly (the zeroing of a done env's older frames is
+// applied when the next input is formed).
+template <class Sys, bool kLn, int S, int W>
+__global__ __launch_bounds__(W * 64) void k_evaluate_policy_attn_f32(KArgs a, PArgs p, EArgs ev) {
+  constexpr int E = 16;
+  constexpr int O = Sys::O, A = Sys::A, ED = O / 2;
+  constexpr int SO = S * O, KS = (SO + 3) / 4;
+  static_assert(kLn || S == 1, "frame stacking is the LayerNorm variant's");
+  static_assert(SO <= kAFMaxIn && O <= kPolMaxObs && A <= kPolMaxAct && ED <= 4, "policy tile shape");
+  constexpr int SZ = SO - O;  // the stack's older frames
+  __shared__ __attribute__((aligned(16))) uint8_t s_lds[kAFLdsBytes];
+  __shared__ double s_norm[2 * kPolMaxObs];
+  const int tid = (int)threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6, G = lane >> 4, col = lane & 15;
+  const bool bad = !blob_is(p.blob, kAFTag, kLn ? LZ_BLOB_ATTN_LN_F32 : LZ_BLOB_ATTN_F32);
+  blob_to_lds(reinterpret_cast<f4v*>(s_lds), reinterpret_cast<const f4v*>(p.blob), kAFExt / 16, tid, W * 64,
+              bad);
+  blob_to_lds(reinterpret_cast<f4v*>(s_lds + kAFExt), reinterpret_cast<const f4v*>(p.blob + kAFLogStd),
+              kAFConst / 16, tid, W * 64, bad);
+  if (tid < O) {
+    s_norm[tid] = p.norm ? p.norm[tid] : 0.0;
+    s_norm[kPolMaxObs + tid] = p.norm ? sqrt(p.norm[O + tid] + p.eps) : 1.0;
+  }
+  const uint64_t tick = *a.tick_in;
+  if (blockIdx.x == 0 && tid == 0) {
+    *a.counter_next = 0;
+    *a.tick_out = tick + a.tick_adv;
+  }
+  const uint8_t* s_ext = s_lds;
+  const float* cst = reinterpret_cast<const float*>(s_lds + kAFExt);
+  const float* g_scale = cst + 4;
+  const float* ttab = cst + 16;
+  const uint8_t* s_net = s_lds + kAFExt + kAFConst;
+  {  // the pi net into the slot: this wave's share of the 100 1-KiB pieces
+    const uint32_t m0_net = __builtin_amdgcn_readfirstlane(
+        (uint32_t)(uintptr_t)(las_p)(const_cast<uint8_t*>(s_net)));
+    const uint8_t* g_pi = p.blob + kAFPi;
+    const int wv = __builtin_amdgcn_readfirstlane(wave);  // M0 takes a wave-uniform SGPR
+    for (int c = wv; c < kAFNet / 1024; c += W)
+      dma16_keep(g_pi + c * 1024 + lane * 16, (uint32_t)__builtin_amdgcn_readfirstlane(m0_net + 1024u * c));
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // this wave's DMA pieces have landed
+  }
+  __syncthreads();
+  const bool norm = p.norm != nullptr;
+  const double* mu = s_norm;
+  const double* sd = s_norm + kPolMaxObs;
+  const bool det = (p.pflags & LZ_POLICY_DETERMINISTIC) != 0;
+  const bool autoreset = (a.flags & LZ_FLAG_AUTORESET) != 0;
+  Sys sys;
+  sys.setup(a);
+  const int64_t ntiles = (a.n + E - 1) / E;
+  // this lane group's fc1 inputs: input 4s + G of the normalised input
+  auto inputs = [&](const float* src, float* xs) {
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      float v = 0.0f;
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        if (4 * s + g < SO) v = G == g ? src[4 * s + g < SO ? 4 * s + g : 0] : v;
+      xs[s] = v;
+    }
+  };
+  // kLn: lane group G holds entries 4s + G (s < KS) of its env's stack (k_rollout_policy_
+  // attn_f32's layout and roll)
+  auto cur_stack = [&](const float* stv, bool z, float* xs) {
+#pragma unroll
+    for (int s = 0; s < KS; ++s) xs[s] = (z && 4 * s + G < SZ) ? 0.0f : stv[s];
+  };
+  auto frame_at = [&](const float* f, int qi) {  // f[qi] for a lane-varying qi in [0, O)
+    float v = 0.0f;
+#pragma unroll
+    for (int j = 0; j < O; ++j) v = qi == j ? f[j] : v;
+    return v;
+  };
+  auto roll_stack = [&](float* stv, const float* nf) {
+    const int src = (((G + O) & 3) << 4) | col;
+    const bool carry = G + (O & 3) >= 4;
+    float nst[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      constexpr int D = O / 4;
+      const float va = __shfl(s + D < KS ? stv[s + D < KS ? s + D : 0] : 0.0f, src, 64);
+      const float vb = __shfl(s + D + 1 < KS ? stv[s + D + 1 < KS ? s + D + 1 : 0] : 0.0f, src, 64);
+      const int qi = 4 * s + G;
+      const float v = carry ? vb : va;
+      nst[s] = qi < SZ ? v : (qi < SO ? frame_at(nf, qi - SZ) : 0.0f);
+    }
+#pragma unroll
+    for (int s = 0; s < KS; ++s) stv[s] = nst[s];
+  };
+  for (int64_t tile = (int64_t)blockIdx.x * W + wave; tile < ntiles; tile += (int64_t)gridDim.x * W) {
+    const int64_t i = tile * E + col;
+    const bool valid = i < a.n;        // all four lanes of the env compute it
+    const bool own = valid && G == 0;  // ... lane group 0 stores it
+    int32_t steps = 0;
+    bool any_reset = false;
+    double q[1][4];  // lane group G's part of this tile's accumulators, zeroed per tile
+    EvalCount c;
+    eval_zero<1>(q, c);
+    float o[O], st[kLn ? KS : 1];
+    bool zf = false;
+#pragma unroll
+    for (int j = 0; j < O; ++j) o[j] = 0.0f;
+    if (valid) {
+      sys.load(a, i);
+      if (a.count_steps) steps = static_cast<const int32_t*>(a.pl[Sys::kStepPlane])[i];
+#pragma unroll
+      for (int j = 0; j < O; ++j) o[j] = p.obs_in[i * O + j];
+    }
+    if constexpr (kLn) {
+#pragma unroll
+      for (int s = 0; s < KS; ++s)
+        st[s] = (valid && 4 * s + G < SO) ? p.stack_in[i * SO + (4 * s + G < SO ? 4 * s + G : 0)] : 0.0f;
+    }
+    for (int k = 0; k < a.K; ++k) {
+      f32x4 F[4];
+      float xs[KS];
+      if constexpr (kLn) {
+        cur_stack(st, zf, xs);
+      } else {
+        float x[O];
+        normalize<O>(o, x, norm, mu, sd, p.clip);
+        inputs(x, xs);
+      }
+      attn16_extract<KS, kLn>(s_ext, xs, lane, F);
+      float mean[A];
+      attn16_net<A>(s_net, F, lane, mean, ttab);
+      float act_c[A];
+#pragma unroll
+      for (int j = 0; j < A; ++j) act_c[j] = 0.0f;
+      if (valid) {  // every lane of the env: the same Philox draw
+        float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (!det) {
+          if constexpr (A <= 2) normal2(a.seed, (uint64_t)(a.gid0 + i), tick + (uint64_t)k, z);
+          else normal4(a.seed, (uint64_t)(a.gid0 + i), tick + (uint64_t)k, z);
+        }
+#pragma unroll
+        for (int j = 0; j < A; ++j) {
+          const float aj = det ? mean[j] : mean[j] + z[j] * g_scale[j];
+          act_c[j] = clip(aj, p.act_lo, p.act_hi);
+        }
+      }
+      if constexpr (kLn) {  // the deferred zeroing of a done env's older frames
+#pragma unroll
+        for (int s = 0; s < KS; ++s) st[s] = (zf && 4 * s + G < SZ) ? 0.0f : st[s];
+      }
+      float on[O], ot[O];
+      float rew = 0.0f;
+      bool did_reset;
+      const uint8_t df = step_body<Sys, float, true, true>(sys, steps, a, i, valid, act_c,
+                                                           tick + (uint64_t)k, k, on, rew, did_reset, ot,
+                                                           G == 0);
+      any_reset = any_reset || did_reset;
+      if (valid) eval_step<1, ED>(q, c, G, ot, rew, df, k, autoreset, ev.skip, ev.max_episodes);
+      if constexpr (kLn) {
+        roll_stack(st, on);
+        zf = df != 0;
+      }
+#pragma unroll
+      for (int j = 0; j < O; ++j) o[j] = on[j];
+    }
+    if (own) {
+#pragma unroll
+      for (int j = 0; j < O; ++j) p.obs_last[i * O + j] = o[j];
+      sys.store(a, i);
+      if (any_reset) sys.store_autoreset_extra(a, i);
+      if (a.count_steps) static_cast<int32_t*>(a.pl[Sys::kStepPlane])[i] = steps;
+    }
+    if (valid) {
+      eval_store<1>(ev.stats, a.n, i, q, c, G, G == 0, bad);
+      if constexpr (kLn) {
+        float xs[KS];
+        cur_stack(st, zf, xs);
+#pragma unroll
+        for (int s = 0; s < KS; ++s)
+          if (4 * s + G < SO) p.stack_out[i * SO + 4 * s + G] = xs[s];
+      }
+    }
+  }
+}
+
 // obs moments: out = (count, column sums, column sums of squares) from the per-wave
 // partials, summed in a fixed order.  One workgroup per column (the column loop ran in
 // a single workgroup before: 22.9 us per collect at 262,144 envs, 2.8% of K=16); the
@@ -2736,11 +3143,53 @@ static int launch_pol_attn_f32(int ln, int n_stack, const KArgs& a, const PArgs&
   return (int)hipGetLastError();
 }
 
+// The evaluation of the float32 MlpPolicy: f32_policy_shape's wave count, one wave per
+// tile (no critic waves to split off: pair = 0)
+PolShape eval_f32_policy_shape(int64_t n, int num_cus, int variant) {
+  PolShape s = f32_policy_shape(n, num_cus, variant);
+  s.pair = 0;
+  return s;
+}
+
+// ... of the float32 attention actor-critics: 16-env waves, 8 per workgroup (two per
+// SIMD), one workgroup per CU
+PolShape eval_attn_f32_policy_shape(int64_t n, int num_cus, int) {
+  PolShape s = {16, 8, 0, 0};
+  const int64_t groups = ((n + 15) / 16 + s.waves - 1) / s.waves;
+  s.grid = (int)(groups < num_cus ? groups : num_cus);
+  return s;
+}
+
+template <class Sys>
+static int launch_eval_f32(const KArgs& a, const PArgs& p, const EArgs& ev, const PolShape& sh,
+                           hipStream_t s) {
+  if (sh.waves == 4)
+    hipLaunchKernelGGL((k_evaluate_policy_f32<Sys, 4>), dim3((unsigned)sh.grid), dim3(4 * 64), 0, s, a, p, ev);
+  else
+    hipLaunchKernelGGL((k_evaluate_policy_f32<Sys, 8>), dim3((unsigned)sh.grid), dim3(8 * 64), 0, s, a, p, ev);
+  return (int)hipGetLastError();
+}
+
+template <class Sys>
+static int launch_eval_attn_f32(int ln, int n_stack, const KArgs& a, const PArgs& p, const EArgs& ev,
+                                const PolShape& sh, hipStream_t s) {
+  if (sh.waves != 8) return (int)hipErrorInvalidValue;  // eval_attn_f32_policy_shape's
+  const dim3 grid((unsigned)sh.grid), block(8 * 64);
+#define LZ_EVAL_ATTN(LN, S_) \
+  hipLaunchKernelGGL((k_evaluate_policy_attn_f32<Sys, LN, S_, 8>), grid, block, 0, s, a, p, ev);
+  if (!ln) { LZ_EVAL_ATTN(false, 1) }
+  else if (n_stack == 4) { LZ_EVAL_ATTN(true, 4) }
+  else if (n_stack == 1) { LZ_EVAL_ATTN(true, 1) }
+  else return (int)hipErrorInvalidValue;
+#undef LZ_EVAL_ATTN
+  return (int)hipGetLastError();
+}
+
 // One entry for every policy rollout: the system picks the Sys type, the kind the
 // launcher; a kind the system list (lz_dispatch.h) does not name for the system is not
 // instantiated for it and refused here (lz_api.cpp refuses it first, with a message).
 int launch_policy(PolicyKind kind, int system, int n_stack, const KArgs& a, const PArgs& p,
-                  const PStepArgs* st, const PolShape& sh, void* stream) {
+                  const PStepArgs* st, const PolShape& sh, void* stream, const EArgs* ev) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   return for_system(system, false, [&](auto tag) -> int {
     using Tag = decltype(tag);
@@ -2768,6 +3217,21 @@ int launch_policy(PolicyKind kind, int system, int n_stack, const KArgs& a, cons
       case PolicyKind::F32MlpStep:
         if constexpr (Tag::runs(PolicyKind::F32MlpStep)) {
           if (st) return launch_step_f32<Sys>(a, p, *st, sh, s);
+        }
+        break;
+      case PolicyKind::EvalF32Mlp:
+        if constexpr (Tag::runs(PolicyKind::EvalF32Mlp)) {
+          if (ev) return launch_eval_f32<Sys>(a, p, *ev, sh, s);
+        }
+        break;
+      case PolicyKind::EvalF32Attn:
+        if constexpr (Tag::runs(PolicyKind::EvalF32Attn)) {
+          if (ev) return launch_eval_attn_f32<Sys>(0, n_stack, a, p, *ev, sh, s);
+        }
+        break;
+      case PolicyKind::EvalF32AttnLn:
+        if constexpr (Tag::runs(PolicyKind::EvalF32AttnLn)) {
+          if (ev) return launch_eval_attn_f32<Sys>(1, n_stack, a, p, *ev, sh, s);
         }
         break;
     }

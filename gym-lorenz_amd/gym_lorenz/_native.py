@@ -138,6 +138,36 @@ class LzPolicyRolloutArgs(ctypes.Structure):
     ]
 
 
+class LzPolicyEvalArgs(ctypes.Structure):
+    """lz_policy_eval_args (lz_evaluate_policy_*_f32)."""
+    _fields_ = [
+        ("K", ctypes.c_int32),
+        ("flags", ctypes.c_uint32),
+        ("blob", ctypes.c_void_p),
+        ("obs_in", ctypes.c_void_p),
+        ("obs_last", ctypes.c_void_p),
+        ("obs_norm", ctypes.c_void_p),
+        ("norm_eps", ctypes.c_double),
+        ("clip_obs", ctypes.c_double),
+        ("act_low", ctypes.c_float),
+        ("act_high", ctypes.c_float),
+        ("skip", ctypes.c_int32),
+        ("max_episodes", ctypes.c_int32),
+        ("stats", ctypes.c_void_p),
+    ]
+
+
+# columns of the evaluation table (lorenz_env.h LZ_EVAL_*): float64 [EVAL_COLS, N]
+(EVAL_ABS_SUM0, EVAL_SQ_SUM0, EVAL_MAX_ABS0) = 0, 4, 8
+(EVAL_N_WIN, EVAL_RET_SUM, EVAL_N_STEPS, EVAL_N_EP, EVAL_EP_RET_SUM, EVAL_EP_RET_SQ,
+ EVAL_EP_LEN_SUM, EVAL_TAIL_RET, EVAL_TAIL_LEN, EVAL_FIRST_DONE, EVAL_DONE_OR,
+ EVAL_N_DONE_STEPS, EVAL_COLS) = range(12, 25)
+EVAL_COLUMNS = ("abs_sum0", "abs_sum1", "abs_sum2", "abs_sum3", "sq_sum0", "sq_sum1", "sq_sum2",
+                "sq_sum3", "max_abs0", "max_abs1", "max_abs2", "max_abs3", "n_win", "ret_sum",
+                "n_steps", "n_ep", "ep_ret_sum", "ep_ret_sq", "ep_len_sum", "tail_ret", "tail_len",
+                "first_done", "done_or", "n_done_steps")
+
+
 class LzVecNorm(ctypes.Structure):
     _fields_ = [
         ("obs_rms", ctypes.c_void_p),
@@ -165,10 +195,12 @@ class LzLaunchShape(ctypes.Structure):
 # lz_get_launch_shape calls / kernels / flags (lorenz_env.h)
 (CALL_STEP, CALL_ROLLOUT, CALL_ROLLOUT_POLICY, CALL_ROLLOUT_POLICY_F32, CALL_POLICY_STEP_F32,
  CALL_ROLLOUT_POLICY_ATTN, CALL_ROLLOUT_POLICY_ATTN_STACK, CALL_ROLLOUT_POLICY_ATTN_F32,
- CALL_ROLLOUT_POLICY_ATTN_STACK_F32, CALL_STEP_NOISE) = range(10)
+ CALL_ROLLOUT_POLICY_ATTN_STACK_F32, CALL_STEP_NOISE, CALL_EVALUATE_POLICY_F32,
+ CALL_EVALUATE_POLICY_ATTN_F32, CALL_EVALUATE_POLICY_ATTN_STACK_F32) = range(13)
 KERNELS = {1: "step", 2: "step_multi", 3: "rollout", 4: "rollout_wave", 5: "rollout_split",
            6: "policy", 7: "policy_pair", 8: "policy_pair_pipe", 9: "policy_split",
-           10: "policy_step", 11: "policy_attn", 12: "policy_attn_f32", 13: "rollout_pair"}
+           10: "policy_step", 11: "policy_attn", 12: "policy_attn_f32", 13: "rollout_pair",
+           14: "eval", 15: "eval_attn_f32"}
 SHAPE_NO_DONE, SHAPE_GRID_STRIDE = 1, 2
 
 VP = ctypes.c_void_p
@@ -239,6 +271,10 @@ _SIGS = {
     "lz_rollout_policy_attn_f32": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyRolloutArgs)]),
     "lz_rollout_policy_attn_stack_f32": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyRolloutArgs),
                                                         ctypes.c_int32, VP, VP]),
+    "lz_evaluate_policy_f32": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyEvalArgs)]),
+    "lz_evaluate_policy_attn_f32": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyEvalArgs)]),
+    "lz_evaluate_policy_attn_stack_f32": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyEvalArgs),
+                                                         ctypes.c_int32, VP, VP]),
     "lz_gae": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, VP, VP, VP, VP, ctypes.c_double,
                               ctypes.c_double, VP, VP, ctypes.c_int32, VP]),
     "lz_episode_starts": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, VP, VP, VP, VP,

@@ -25,6 +25,12 @@ statistics frozen for the K steps and update them once from the pooled moments.
 ``compute_returns_and_advantage`` is ``lz_gae``.  The buffers come back as
 time-major device tensors in SB3's RolloutBuffer layout ([K, N, ...]).
 
+``FusedEvaluator.evaluate(K)`` is what the reference does with a trained policy
+afterwards (its ``test_evaluate.py`` scripts, SB3 ``evaluate_policy``): the same closed
+loop without the value net, the bootstrap and the [K, N, *] buffers, the MAE / RMSE /
+episode-return statistics kept as per-env float64 running sums on the device
+(``lz_evaluate_policy_f32`` / ``_attn_f32`` / ``_attn_stack_f32``).
+
 ``ActorCriticMlp`` is a plain-torch restatement of SB3's ActorCriticPolicy for this
 net_arch (same state_dict keys, same orthogonal init) -- the weight source when SB3 is
 absent and the fp32 reference in the tests.  An SB3 policy's ``state_dict()`` can be
@@ -796,3 +802,230 @@ class FusedRolloutCollector:
                                  ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
         batch.advantages, batch.returns = adv, ret
         return adv, ret
+
+
+# ------------------------------------------------------------------------------ evaluation
+# The factor the reference's evaluators multiply the error observations by before they
+# take MAE / RMSE: HRSyncEnv emits e / 50 and code/test_evaluate.py:124-126,137 multiplies
+# it back; the other systems' observations carry the error itself.
+ERR_SCALE = {"lorenz3": 1.0, "lorenz4": 1.0, "pmsm": 1.0, "hr": 50.0}
+ERR_DIMS = {"lorenz3": 3, "lorenz4": 4, "pmsm": 3, "hr": 3}
+
+
+class EvalResult:
+    """What one ``FusedEvaluator.evaluate`` launch wrote: ``stats``, the float64 device
+    table [EVAL_COLS, N] of lorenz_env.h's LZ_EVAL_* columns (``res.n_win``,
+    ``res.ret_sum`` ... are its rows by name, ``res.columns`` all of them), and the pooled
+    figures the reference's evaluators print.
+
+    ``pooled_sums`` is the float64 device tensor [EVAL_COLS] of column sums over this
+    handle's envs; a multi-rank caller all-reduces it (SUM) and passes it back through
+    ``EvalResult.pool``.  The max / first-done / done-bit columns do not pool by a sum:
+    ``max_abs`` is taken over the table itself."""
+
+    def __init__(self, stats, system_name):
+        self.stats = stats
+        self.system_name = system_name
+        self.err_dims = ERR_DIMS[system_name]
+        self.err_scale = ERR_SCALE[system_name]
+        self.pooled_sums = stats.sum(dim=1)
+        self.columns = {name: stats[i] for i, name in enumerate(nat.EVAL_COLUMNS)}
+        self._pooled = None
+
+    def __getattr__(self, name):
+        cols = self.__dict__.get("columns")
+        if cols is not None and name in cols:
+            return cols[name]
+        raise AttributeError(name)
+
+    def pool(self, pooled_sums=None):
+        """The pooled figures as a dict of Python floats / lists (one device-to-host copy),
+        from ``pooled_sums`` (default: this handle's own)."""
+        s = (self.pooled_sums if pooled_sums is None else pooled_sums).cpu().numpy()
+        ED, c = self.err_dims, self.err_scale
+        nan = float("nan")
+        n_win = s[nat.EVAL_N_WIN]
+        ab = s[nat.EVAL_ABS_SUM0:nat.EVAL_ABS_SUM0 + ED]
+        sq = s[nat.EVAL_SQ_SUM0:nat.EVAL_SQ_SUM0 + ED]
+        out = {}
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["mae_per_dim"] = [float(c * v / n_win) if n_win else nan for v in ab]
+            out["rmse_per_dim"] = [float(c * np.sqrt(v / n_win)) if n_win else nan for v in sq]
+            out["mae"] = float(c * ab.sum() / (ED * n_win)) if n_win else nan
+            out["rmse"] = float(c * np.sqrt(sq.sum() / (ED * n_win))) if n_win else nan
+            n_ep = s[nat.EVAL_N_EP]
+            if n_ep:
+                mean = s[nat.EVAL_EP_RET_SUM] / n_ep
+                out["mean_reward"] = float(mean)
+                out["std_reward"] = float(np.sqrt(max(s[nat.EVAL_EP_RET_SQ] / n_ep - mean * mean, 0.0)))
+                out["mean_ep_length"] = float(s[nat.EVAL_EP_LEN_SUM] / n_ep)
+            else:
+                out["mean_reward"] = out["std_reward"] = out["mean_ep_length"] = nan
+            n_steps = s[nat.EVAL_N_STEPS]
+            out["mean_step_reward"] = float(s[nat.EVAL_RET_SUM] / n_steps) if n_steps else nan
+        return out
+
+    def _get(self, key):
+        if self._pooled is None:
+            self._pooled = self.pool()
+        return self._pooled[key]
+
+    mae = property(lambda self: self._get("mae"))
+    rmse = property(lambda self: self._get("rmse"))
+    mae_per_dim = property(lambda self: self._get("mae_per_dim"))
+    rmse_per_dim = property(lambda self: self._get("rmse_per_dim"))
+    mean_reward = property(lambda self: self._get("mean_reward"))
+    std_reward = property(lambda self: self._get("std_reward"))
+    mean_ep_length = property(lambda self: self._get("mean_ep_length"))
+    mean_step_reward = property(lambda self: self._get("mean_step_reward"))
+
+    @property
+    def max_abs(self):
+        """Largest |error| in the window over envs and error dims (NaN if any is NaN)."""
+        m = self.stats[nat.EVAL_MAX_ABS0:nat.EVAL_MAX_ABS0 + self.err_dims]
+        return float(self.err_scale * m.max().item())  # torch.max propagates NaN
+
+
+class FusedEvaluator:
+    """The reference's evaluation loops on the device, one launch per evaluation
+    (lz_evaluate_policy_f32 / _attn_f32 / _attn_stack_f32): K steps of {frozen
+    VecNormalize, policy forward at SB3's float32 precision, (sample,) clip, env step}
+    with per-env float64 running sums of |error|, error^2, max |error|, rewards and episode
+    returns in registers -- no [K, N, *] buffer, no value net -- and one [EVAL_COLS, N]
+    table at the end (code/test_evaluate.py:91-150, verify_sync.py:208-237,
+    code/lorenz_filter/test_evaluate.py:94-157, code/lorenz_pmsm/test_evaluate.py:61-166).
+
+    backend:       gym_lorenz.core.BatchedEnv, float32 (lorenz3 / lorenz4 / pmsm / hr; the
+                   attention policies: lorenz3 / pmsm / hr)
+    state_dict:    SB3 ActorCriticPolicy state_dict; its keys pick the kernel as
+                   FusedRolloutCollector.set_params does (MlpPolicy, code/train.py's
+                   attention extractor, code/lorenz_filter/train.py's LayerNorm one)
+    obs_rms:       DeviceRunningMeanStd whose statistics stay frozen, or None
+    deterministic: SB3 predict(deterministic=True) (default); False draws the Philox
+                   normals a rollout would
+    frame_stack:   1 or 4 (VecFrameStack in front of the LayerNorm attention policy)
+    """
+
+    def __init__(self, backend, state_dict, obs_rms=None, clip_obs=10.0, norm_eps=1e-8,
+                 deterministic=True, frame_stack=1):
+        if backend.tdtype != torch.float32:
+            raise ValueError("the fused evaluation runs float32 env handles")
+        if backend.system_name not in ERR_SCALE:
+            raise ValueError("the fused evaluation runs LORENZ3 / LORENZ4 / PMSM / HR")
+        self.env = backend
+        self.device = backend.device
+        self.n, self.O, self.A = backend.num_envs, backend.obs_dim, backend.action_dim
+        self.obs_rms, self.clip_obs, self.norm_eps = obs_rms, float(clip_obs), float(norm_eps)
+        self.deterministic = bool(deterministic)
+        self.act_low, self.act_high = action_bounds(backend.system_name)
+        self.frame_stack = int(frame_stack)
+        if self.frame_stack not in (1, 4):
+            raise ValueError("frame_stack must be 1 or 4 (the fused kernel's instantiations)")
+        if self.frame_stack > 1 and obs_rms is not None:
+            raise ValueError("the frame-stacked evaluation stacks raw observations (no VecNormalize)")
+        self.last_obs = None
+        self.last_stack = None
+        self.set_params(state_dict)
+
+    def set_params(self, state_dict):
+        """Pack and upload the policy; the blob's format tag is checked on the host against
+        the launch this evaluator makes."""
+        self.attention = is_attention_policy(state_dict)
+        self.attention_ln = is_attention_ln_policy(state_dict)
+        if self.frame_stack > 1 and not self.attention_ln:
+            raise ValueError("frame_stack > 1 runs code/lorenz_filter/train.py's policy "
+                             "(the residual + LayerNorm attention extractor)")
+        if self.attention_ln:
+            if self.obs_rms is not None:
+                raise ValueError("the LayerNorm attention evaluation takes raw observations")
+            blob = pack_attn_ln_policy_f32(state_dict, self.frame_stack * self.O, self.A)
+        elif self.attention:
+            blob = pack_attn_policy_f32(state_dict, self.O, self.A)
+        else:
+            blob = pack_policy_f32(state_dict, self.O, self.A)
+        self._set_blob(blob)
+
+    def _set_blob(self, blob):
+        want = blob_format(self.attention, self.attention_ln, False)
+        got = int(nat.lib.lz_policy_blob_format(blob.ctypes.data, blob.size))
+        if got != want:
+            raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "policy blob format %d, the launch "
+                                     "expects %d" % (got, want))
+        self.blob = torch.from_numpy(blob).to(self.device)
+
+    def reset(self, init=None):
+        """VecEnv.reset() (init: injected initial states [N, init_dim], as lz_reset); the
+        next evaluation starts from these observations and a fresh frame stack."""
+        obs = self.env.reset(init=init)
+        self.last_obs = obs.clone()
+        self.last_stack = torch.zeros((self.n, self.frame_stack * self.O), dtype=torch.float32,
+                                      device=self.device)
+        self.last_stack[:, -self.O:] = obs
+        return self.last_obs
+
+    def evaluate(self, K, skip=0, max_episodes=0):
+        """K closed-loop steps in one launch -> EvalResult.  skip: in-episode step index
+        from which the error window opens (the reference's ``step >= 1000``);
+        max_episodes: episodes counted per env (0: every step counts)."""
+        if self.last_obs is None:
+            self.reset()
+        n, O, dev = self.n, self.O, self.device
+        stats = torch.empty((nat.EVAL_COLS, n), dtype=torch.float64, device=dev)
+        obs_last = torch.empty((n, O), dtype=torch.float32, device=dev)
+        e = nat.LzPolicyEvalArgs()
+        e.K = int(K)
+        e.flags = nat.POLICY_DETERMINISTIC if self.deterministic else 0
+        e.blob, e.obs_in, e.obs_last = _p(self.blob), _p(self.last_obs), _p(obs_last)
+        e.obs_norm = _p(self.obs_rms.state) if self.obs_rms is not None else None
+        e.norm_eps, e.clip_obs = self.norm_eps, self.clip_obs
+        e.act_low, e.act_high = self.act_low, self.act_high
+        e.skip, e.max_episodes = int(skip), int(max_episodes)
+        e.stats = _p(stats)
+        # the launch runs on the env handle's stream: order the caller's current stream
+        # (where blob / last_obs were written and the table is read) around it both ways
+        caller = torch.cuda.current_stream(dev)
+        es = self.env.stream
+        if es != caller:
+            es.wait_stream(caller)
+        stack_out = None
+        if self.attention_ln:
+            stack_out = torch.empty((n, self.frame_stack * O), dtype=torch.float32, device=dev)
+            nat.check(nat.lib.lz_evaluate_policy_attn_stack_f32(
+                self.env._h, ctypes.byref(e), self.frame_stack, _p(self.last_stack), _p(stack_out)))
+        elif self.attention:
+            nat.check(nat.lib.lz_evaluate_policy_attn_f32(self.env._h, ctypes.byref(e)))
+        else:
+            nat.check(nat.lib.lz_evaluate_policy_f32(self.env._h, ctypes.byref(e)))
+        if es != caller:
+            caller.wait_stream(es)
+        self._keep = (self.blob, self.last_obs, self.last_stack)  # alive until consumed
+        self.last_obs = obs_last
+        if stack_out is not None:
+            self.last_stack = stack_out
+        return EvalResult(stats, self.env.system_name)
+
+
+def evaluate_policy(backend, state_dict, n_eval_episodes, **kw):
+    """SB3 ``evaluate_policy(model, env, n_eval_episodes)`` (code/gym_run.py:95) on an
+    auto-reset handle with ``max_episode_steps = L > 0``: every env runs
+    ``max_episodes = ceil(n_eval_episodes / N)`` whole episodes in one launch of
+    ``K = max_episodes * L`` steps; returns ``(mean_reward, std_reward)`` over the counted
+    episodes, std = sqrt(max(sum(R^2)/n - mean^2, 0)).
+
+    SB3 takes n_eval_episodes / N episodes from each of the N envs, so this is SB3's
+    episode set when N divides n_eval_episodes; otherwise this raises.  (Episodes that
+    terminate before L steps are counted as they end; an env that finishes its share early
+    keeps stepping uncounted.)  **kw: FusedEvaluator's arguments."""
+    n = backend.num_envs
+    L = int(backend.config.max_episode_steps)
+    if not (backend.config.flags & nat.FLAG_AUTORESET) or L <= 0:
+        raise ValueError("evaluate_policy needs an auto-reset handle with max_episode_steps > 0")
+    n_eval_episodes = int(n_eval_episodes)
+    if n_eval_episodes < 1 or n_eval_episodes % n:
+        raise ValueError("n_eval_episodes (%d) must be a positive multiple of the %d envs"
+                         % (n_eval_episodes, n))
+    per_env = -(-n_eval_episodes // n)
+    ev = FusedEvaluator(backend, state_dict, **kw)
+    ev.reset()
+    res = ev.evaluate(per_env * L, skip=0, max_episodes=per_env)
+    return res.mean_reward, res.std_reward

@@ -55,6 +55,13 @@
  *          residual/LayerNorm extractor)
  *   lz_frame_stack
  *       -> SB3 VecFrameStack.step_wait (code/lorenz_filter/train.py:115)
+ *   lz_evaluate_policy_f32 / lz_evaluate_policy_attn_f32 / lz_evaluate_policy_attn_stack_f32
+ *       -> the evaluators' deterministic closed loops and their statistics:
+ *          code/test_evaluate.py:91-150 (HR, attention policy, MAE / RMSE of obs[:3]*50
+ *          over step >= 1000), code/gym-lorenz/gym_lorenz/envs/verify_sync.py:208-237,
+ *          code/lorenz_filter/test_evaluate.py:94-157 (LayerNorm attention policy on
+ *          VecFrameStack(4)), code/lorenz_pmsm/test_evaluate.py:61-166 (PMSM behind frozen
+ *          VecNormalize) and SB3 evaluate_policy (code/gym_run.py:95)
  *
  * Conventions
  *   - Every function returns an lz_status (0 == LZ_OK).  Nothing throws across
@@ -567,6 +574,91 @@ lz_status lz_rollout_policy_attn_stack_f32(lz_handle* h, const lz_policy_rollout
                                            int32_t n_stack, const float* stack_in,
                                            float* stack_out);
 
+/* ------------------------------------------------------------------------------
+ * Fused policy evaluation.  What the reference does with a trained policy: a closed loop
+ * of K steps {normalise obs, policy forward, (sample,) clip, env step} and, per env, the
+ * mean absolute error / RMSE of the synchronisation error over the steady part of the run
+ * (code/test_evaluate.py:91-150 -- HR, 10 x 5000 steps, obs[:3]*50 over step >= 1000;
+ * code/gym-lorenz/gym_lorenz/envs/verify_sync.py:208-237; code/lorenz_filter/
+ * test_evaluate.py:94-157; code/lorenz_pmsm/test_evaluate.py:61-166 -- the eight A2C
+ * policies behind frozen VecNormalize, 2000 steps) or SB3's mean / std of the episode
+ * returns (code/gym_run.py:95 evaluate_policy(model, env, n_eval_episodes=10)).  One
+ * launch runs the K steps with the env state, the policy activations and float64
+ * accumulators in registers -- no per-step store, no value net -- and writes one
+ * plane-major table stats double [LZ_EVAL_COLS, N] at the end.
+ *
+ * Per env, every call starts with t = ep = 0, ep_ret = 0.0, ep_len = 0.  Step k = 0 ..
+ * K-1 emits o (the float32 observation before any auto-reset: on a done step the
+ * terminal observation, what env.step returns in the reference), r (the float32 env
+ * reward, never bootstrapped) and d (LZ_DONE_* bits):
+ *   counted = max_episodes == 0 || ep < max_episodes      (uncounted steps still run)
+ *   if counted: RET_SUM += (double)r; N_STEPS += 1; ep_ret += (double)r; ep_len += 1
+ *   if counted and t >= skip: for each error dim j < ED (the leading error components of
+ *       the observation: 3 for LORENZ3 / PMSM / HR, 4 for LORENZ4; columns j >= ED stay 0)
+ *       a = (double)fabsf(o[j]); ABS_SUM[j] += a; SQ_SUM[j] += a * a;
+ *       MAX_ABS[j] = (a > MAX_ABS[j] || isnan(a)) ? a : MAX_ABS[j]      (NaN is sticky)
+ *     and N_WIN += 1
+ *   t += 1
+ *   if d != 0: DONE_OR |= d; N_DONE_STEPS += 1; FIRST_DONE = k if it is still -1; with
+ *     LZ_FLAG_AUTORESET: if counted { N_EP += 1; EP_RET_SUM += ep_ret; EP_RET_SQ +=
+ *     ep_ret * ep_ret; EP_LEN_SUM += ep_len }, then ep += 1, t = ep_ret = ep_len = 0
+ *     (without auto-reset nothing restarts: the env keeps stepping, as the reference's
+ *     evaluators do)
+ * and at the end TAIL_RET = ep_ret, TAIL_LEN = ep_len (the unfinished counted episode,
+ * or the whole run without auto-reset).  HR's error dims are e / 50 (lorenz_env_try.py's
+ * scale): the table holds the raw observation components.
+ * ------------------------------------------------------------------------------ */
+enum {
+  LZ_EVAL_ABS_SUM0 = 0, LZ_EVAL_ABS_SUM1 = 1, LZ_EVAL_ABS_SUM2 = 2, LZ_EVAL_ABS_SUM3 = 3,
+  LZ_EVAL_SQ_SUM0 = 4, LZ_EVAL_SQ_SUM1 = 5, LZ_EVAL_SQ_SUM2 = 6, LZ_EVAL_SQ_SUM3 = 7,
+  LZ_EVAL_MAX_ABS0 = 8, LZ_EVAL_MAX_ABS1 = 9, LZ_EVAL_MAX_ABS2 = 10, LZ_EVAL_MAX_ABS3 = 11,
+  LZ_EVAL_N_WIN = 12,
+  LZ_EVAL_RET_SUM = 13,
+  LZ_EVAL_N_STEPS = 14,
+  LZ_EVAL_N_EP = 15,
+  LZ_EVAL_EP_RET_SUM = 16,
+  LZ_EVAL_EP_RET_SQ = 17,
+  LZ_EVAL_EP_LEN_SUM = 18,
+  LZ_EVAL_TAIL_RET = 19,
+  LZ_EVAL_TAIL_LEN = 20,
+  LZ_EVAL_FIRST_DONE = 21,
+  LZ_EVAL_DONE_OR = 22,
+  LZ_EVAL_N_DONE_STEPS = 23,
+  LZ_EVAL_COLS = 24
+};
+
+typedef struct lz_policy_eval_args {
+  int32_t K;               /* steps, >= 1 */
+  uint32_t flags;          /* LZ_POLICY_DETERMINISTIC; LZ_POLICY_BOOTSTRAP is LZ_ERR_INVALID,
+                              LZ_POLICY_I8X4 LZ_ERR_UNSUPPORTED */
+  const void* blob;        /* device copy of the packed float32 policy */
+  const float* obs_in;     /* [N, O] raw obs the evaluation starts from */
+  float* obs_last;         /* [N, O] raw obs after the K steps (may alias obs_in) */
+  const double* obs_norm;  /* frozen VecNormalize obs_rms [mean(O), var(O)] or NULL */
+  double norm_eps, clip_obs;
+  float act_low, act_high; /* action space Box bounds */
+  int32_t skip;            /* first step index of an episode inside the error window, >= 0 */
+  int32_t max_episodes;    /* episodes counted per env; 0 = every step counts */
+  double* stats;           /* [LZ_EVAL_COLS, N] device, written once when the K steps are done */
+} lz_policy_eval_args;
+
+/* The evaluation launch for an lz_policy_pack_f32 blob (LORENZ3 / LORENZ4 / PMSM / HR;
+ * code/lorenz_pmsm/test_evaluate.py:117-120's loop, code/gym_run.py:95), an
+ * lz_attn_policy_pack_f32 blob (LORENZ3 / PMSM / HR; code/test_evaluate.py:91-150,
+ * verify_sync.py:208-237) and an lz_attn_ln_policy_pack_f32 blob on VecFrameStack(n_stack)
+ * observations (n_stack 1 or 4, obs_norm NULL; code/lorenz_filter/test_evaluate.py:94-157;
+ * stack_in / stack_out as lz_rollout_policy_attn_stack).  Float32 Euler handles only.
+ * Everything but the outputs is the rollout's: the actions (and a stochastic evaluation's
+ * Philox normals) are those of lz_rollout_policy_*_f32 without LZ_POLICY_BOOTSTRAP, the
+ * state planes and step counters are stored at the end, the tick advances by K and the
+ * call parity flips (one of "these calls" of the hipGraph note above).  A blob of another
+ * format gives an all-NaN table. */
+lz_status lz_evaluate_policy_f32(lz_handle* h, const lz_policy_eval_args* e);
+lz_status lz_evaluate_policy_attn_f32(lz_handle* h, const lz_policy_eval_args* e);
+lz_status lz_evaluate_policy_attn_stack_f32(lz_handle* h, const lz_policy_eval_args* e,
+                                            int32_t n_stack, const float* stack_in,
+                                            float* stack_out);
+
 /* SB3 RolloutBuffer.compute_returns_and_advantage over time-major [K, N] float32
  * buffers (float32 arithmetic in NumPy's order): advantages and returns out.
  * done = the done bytes of each step (episode_starts shifted by one). */
@@ -731,8 +823,11 @@ enum {
   LZ_CALL_ROLLOUT_POLICY_ATTN_STACK = 6,   /* lz_rollout_policy_attn_stack */
   LZ_CALL_ROLLOUT_POLICY_ATTN_F32 = 7,     /* lz_rollout_policy_attn_f32 */
   LZ_CALL_ROLLOUT_POLICY_ATTN_STACK_F32 = 8, /* lz_rollout_policy_attn_stack_f32 */
-  LZ_CALL_STEP_NOISE = 9                   /* lz_step with caller-supplied noise (always
+  LZ_CALL_STEP_NOISE = 9,                  /* lz_step with caller-supplied noise (always
                                               k_step: the multi-tile kernel draws on device) */
+  LZ_CALL_EVALUATE_POLICY_F32 = 10,        /* lz_evaluate_policy_f32 */
+  LZ_CALL_EVALUATE_POLICY_ATTN_F32 = 11,   /* lz_evaluate_policy_attn_f32 */
+  LZ_CALL_EVALUATE_POLICY_ATTN_STACK_F32 = 12 /* lz_evaluate_policy_attn_stack_f32 */
 };
 enum {
   LZ_KERNEL_STEP = 1,             /* k_step: one 256-env tile per workgroup */
@@ -747,8 +842,10 @@ enum {
   LZ_KERNEL_POLICY_STEP = 10,     /* k_policy_step_f32 */
   LZ_KERNEL_POLICY_ATTN = 11,     /* k_rollout_policy<..., kAttn / kAttnLn> (bf16) */
   LZ_KERNEL_POLICY_ATTN_F32 = 12, /* k_rollout_policy_attn_f32 */
-  LZ_KERNEL_ROLLOUT_PAIR = 13     /* k_rollout_pair: PMSM, the step split over a lane
+  LZ_KERNEL_ROLLOUT_PAIR = 13,    /* k_rollout_pair: PMSM, the step split over a lane
                                      pair (SysPMSM::step_pair) */
+  LZ_KERNEL_EVAL = 14,            /* k_evaluate_policy_f32: one wave per 32-env tile, pi net only */
+  LZ_KERNEL_EVAL_ATTN_F32 = 15    /* k_evaluate_policy_attn_f32: 16-env waves, pi net resident */
 };
 #define LZ_SHAPE_NO_DONE 1u     /* the done-free instantiation (no done can occur) */
 #define LZ_SHAPE_GRID_STRIDE 2u /* fewer workgroups than env groups: workgroups loop */
