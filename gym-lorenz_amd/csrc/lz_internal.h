@@ -552,7 +552,7 @@ PolShape f32_policy_shape(int64_t n, int num_cus, int variant);
 // (one per SIMD: the 137 KB blob leaves room for one workgroup per CU)
 PolShape attn_policy_shape(int64_t n, int num_cus, int variant);
 // the attention actor-critics in float32 (kAF* blob), code/train.py's extractor and the
-// residual + LayerNorm variant alike: 16 envs per wave, 8 or 4 waves
+// residual + LayerNorm variant alike: 16 envs per wave, 8 waves
 PolShape attn_f32_policy_shape(int64_t n, int num_cus, int variant);
 // Launch the rollout of `kind` for `system` (lz_config.system: the Euler systems);
 // hipErrorInvalidValue where the kind (or LZ_POLICY_I8X4 in F32Mlp) is not built for the

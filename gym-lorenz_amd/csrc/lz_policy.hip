@@ -1018,6 +1018,132 @@ __device__ __forceinline__ void value_fwd(const uint8_t* blob, const uint8_t* vf
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// The steps every policy kernel shares, written once.
+
+// Launch prologue: VecNormalize's mean and sqrt(var + eps) per obs dim into s_norm (LDS:
+// mean at [0, O), scale at [kPolMaxObs, kPolMaxObs + O)), and the tick protocol -- read
+// this launch's tick, zero the done cursor and publish the next launch's tick.  The
+// caller's __syncthreads() follows.
+template <int O>
+__device__ __forceinline__ uint64_t pol_prologue(const KArgs& a, const PArgs& p, double* s_norm, int tid) {
+  if (tid < O) {
+    s_norm[tid] = p.norm ? p.norm[tid] : 0.0;
+    s_norm[kPolMaxObs + tid] = p.norm ? sqrt(p.norm[O + tid] + p.eps) : 1.0;
+  }
+  const uint64_t tick = *a.tick_in;
+  if (blockIdx.x == 0 && tid == 0) {
+    *a.counter_next = 0;
+    *a.tick_out = tick + a.tick_adv;
+  }
+  return tick;
+}
+
+// The action head, in three pieces.  cst = the packer's torch.distributions.Normal
+// constants (LDS, wave-uniform broadcast reads): scale = exp(log_std) at cst[0..3],
+// 2 * scale**2 at cst[4..7], log(scale) at cst[8..11].
+// The standard-normal draw of env i at Philox tick t (zeros when deterministic):
+template <int A>
+__device__ __forceinline__ void policy_draw(const KArgs& a, int64_t i, uint64_t t, bool det, float* z) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) z[j] = 0.0f;
+  if (!det) {
+    if constexpr (A <= 2) normal2(a.seed, (uint64_t)(a.gid0 + i), t, z);
+    else normal4(a.seed, (uint64_t)(a.gid0 + i), t, z);
+  }
+}
+// Normal.rsample of component j (the mean when deterministic) ...
+__device__ __forceinline__ float normal_rsample(float mean, float z, const float* cst, int j, bool det) {
+  return det ? mean : mean + z * cst[j];
+}
+// ... and Normal(mean, scale_j).log_prob(aj)
+__device__ __forceinline__ float normal_logp(float aj, float mean, const float* cst, int j) {
+  const float d = aj - mean;
+  return (-(d * d)) / cst[4 + j] - cst[8 + j] - 0.91893853320467274f;
+}
+
+// The whole head for env i: act = the sample, act_c = np.clip(act, low, high) and, kLogp,
+// the returned sum_j log_prob(act_j).  Two kernels keep this loop in place, around the same
+// three pieces, because they measured slower calling it: k_policy_step_f32 (its PMSM kernel
+// spills 20 VGPRs for 15, the collect 0.8 % slower) and k_rollout_policy (with the act[]
+// array the compiler moves a private array of the HR 8-wave kernels to LDS, 8 KiB more:
+// bf16 at 65,536 envs 1.35 % slower, i8x4 at 262,144 0.3 %).
+template <int A, bool kLogp>
+__device__ __forceinline__ float policy_sample(const KArgs& a, const PArgs& p, int64_t i, uint64_t t,
+                                               bool det, const float* mean, const float* cst, float* act,
+                                               float* act_c) {
+  float z[4];
+  policy_draw<A>(a, i, t, det, z);
+  float lp = 0.0f;
+#pragma unroll
+  for (int j = 0; j < A; ++j) {
+    const float aj = normal_rsample(mean[j], z[j], cst, j, det);
+    if constexpr (kLogp) {
+      const float lpj = normal_logp(aj, mean[j], cst, j);
+      lp = j == 0 ? lpj : lp + lpj;
+    }
+    act[j] = aj;
+    act_c[j] = clip(aj, p.act_lo, p.act_hi);
+  }
+  return lp;
+}
+
+// SB3: an episode that ended by the time limit alone (rewards += gamma * V(terminal obs))
+__device__ __forceinline__ bool is_truncation(uint32_t df) {
+  return (df & LZ_DONE_TRUNCATED) && !(df & LZ_DONE_TERMINATED);
+}
+
+// Tile open: the env's state planes and step counter into registers (state_open), and the
+// raw observation the previous launch left (zeros for a lane that is not live).
+template <class Sys>
+__device__ __forceinline__ void state_open(Sys& sys, const KArgs& a, int64_t i, bool live, int32_t& steps) {
+  steps = 0;
+  if (live) {
+    sys.load(a, i);
+    if (a.count_steps) steps = static_cast<const int32_t*>(a.pl[Sys::kStepPlane])[i];
+  }
+}
+
+template <class Sys>
+__device__ __forceinline__ void tile_open(Sys& sys, const KArgs& a, const PArgs& p, int64_t i, bool live,
+                                          int32_t& steps, float* o) {
+  state_open(sys, a, i, live, steps);
+#pragma unroll
+  for (int j = 0; j < Sys::O; ++j) o[j] = live ? p.obs_in[i * Sys::O + j] : 0.0f;
+}
+
+// Tile close: the raw observation for the next launch, the state planes (the auto-reset
+// extras only if the env reset during the launch) and the step counter.
+template <class Sys>
+__device__ __forceinline__ void tile_close(Sys& sys, const KArgs& a, const PArgs& p, int64_t i, bool live,
+                                           int32_t steps, bool any_reset, const float* o) {
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < Sys::O; ++j) p.obs_last[i * Sys::O + j] = o[j];
+    sys.store(a, i);
+    if (any_reset) sys.store_autoreset_extra(a, i);
+    if (a.count_steps) static_cast<int32_t*>(a.pl[Sys::kStepPlane])[i] = steps;
+  }
+}
+
+// Fixed-order butterfly over the wave (deterministic): every lane gets the total.
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// The wave's obs-moment partial (O sums, then O sums of squares) from the register
+// accumulators: the lanes with half == 0 hold the sums, half == 1 the squares.
+template <int O>
+__device__ __forceinline__ void moments_store(double* dst, const double* mom_r, int half, int lane) {
+#pragma unroll
+  for (int j = 0; j < 2 * O; ++j) {
+    const double v = wave_sum((j < O ? half == 0 : half == 1) ? mom_r[j < O ? j : j - O] : 0.0);
+    if (lane == 0) dst[j] = v;
+  }
+}
+
 // kPair (see kMlpSerial ...): kMlpPair = mlp_pair, kMlpPairPipe = mlp_pair_pipe,
 // kAttn = attn_extract + attn_nets_pair (kAtt* blob), kAttnLn = attn_ln_extract +
 // attn_nets_pair (kLn* blob) with the S-frame stack in the registers of both lane
@@ -1050,28 +1176,16 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy(KArgs a, PArgs p) {
     blob_to_lds(reinterpret_cast<f4v*>(s_blob), reinterpret_cast<const f4v*>(p.blob), kBlob / 16,
                 tid, W * 64, bad);
   }
-  if (tid < O) {  // VecNormalize: mean and sqrt(var + eps) per obs dim
-    s_norm[tid] = p.norm ? p.norm[tid] : 0.0;
-    s_norm[kPolMaxObs + tid] = p.norm ? sqrt(p.norm[O + tid] + p.eps) : 1.0;
-  }
-  const uint64_t tick = *a.tick_in;
-  if (blockIdx.x == 0 && tid == 0) {
-    *a.counter_next = 0;
-    *a.tick_out = tick + a.tick_adv;
-  }
+  const uint64_t tick = pol_prologue<O>(a, p, s_norm, tid);
   __syncthreads();
   const uint8_t* pi_net = s_blob + (kPair == kAttnLn ? kLnPi : kPair == kAttn ? kAttPi : 0);
   const uint8_t* vf_net =
       s_blob + (kPair == kAttnLn ? kLnVf : kPair == kAttn ? kAttVf : mlp_f32_kind(kPair) ? kF32Net : kPolNet);
-  // torch.distributions.Normal constants, computed by the packer: scale = exp(log_std),
-  // 2 * scale**2, log(scale) (LDS, wave-uniform broadcast reads)
-  const float* g_scale =
+  const float* g_scale =  // policy_sample's Normal constants
       reinterpret_cast<const float*>(
           s_blob + (kPair == kAttnLn   ? kLnLogStd
                     : kPair == kAttn   ? kAttLogStd
                     : mlp_f32_kind(kPair) ? kF32LogStd : kPolLogStd)) + 4;
-  const float* g_var2 = g_scale + 4;
-  const float* g_lscale = g_scale + 8;
   const bool norm = p.norm != nullptr;
   const double* mu = s_norm;
   const double* sd = s_norm + kPolMaxObs;
@@ -1100,17 +1214,10 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy(KArgs a, PArgs p) {
   for (int64_t tile = (int64_t)blockIdx.x * W + wave; tile < ntiles; tile += (int64_t)gridDim.x * W) {
     const int64_t i = tile * E + slot;
     const bool live = owner && i < a.n;
-    int32_t steps = 0;
+    int32_t steps;
     bool any_reset = false;
     float o[O];
-#pragma unroll
-    for (int j = 0; j < O; ++j) o[j] = 0.0f;
-    if (live) {
-      sys.load(a, i);
-      if (a.count_steps) steps = static_cast<const int32_t*>(a.pl[Sys::kStepPlane])[i];
-#pragma unroll
-      for (int j = 0; j < O; ++j) o[j] = p.obs_in[i * O + j];
-    }
+    tile_open(sys, a, p, i, live, steps, o);
     const bool valid = i < a.n;  // kAttnLn: both halves of the env's lanes
     float st[kPair == kAttnLn ? SO : 1];
     if constexpr (kPair == kAttnLn) {
@@ -1176,17 +1283,13 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy(KArgs a, PArgs p) {
       }
       float act_c[A];
       if (live) {
-        float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (!det) {
-          if constexpr (A <= 2) normal2(a.seed, (uint64_t)(a.gid0 + i), tick + (uint64_t)k, z);
-          else normal4(a.seed, (uint64_t)(a.gid0 + i), tick + (uint64_t)k, z);
-        }
+        float z[4];  // policy_sample's loop in place (see there)
+        policy_draw<A>(a, i, tick + (uint64_t)k, det, z);
         float lp = 0.0f;
 #pragma unroll
         for (int j = 0; j < A; ++j) {
-          const float aj = det ? mean[j] : mean[j] + z[j] * g_scale[j];  // Normal.rsample
-          const float d = aj - mean[j];
-          const float lpj = (-(d * d)) / g_var2[j] - g_lscale[j] - 0.91893853320467274f;
+          const float aj = normal_rsample(mean[j], z[j], g_scale, j, det);
+          const float lpj = normal_logp(aj, mean[j], g_scale, j);
           lp = j == 0 ? lpj : lp + lpj;
           act_c[j] = clip(aj, p.act_lo, p.act_hi);
           p.act[off * A + j] = aj;
@@ -1220,7 +1323,7 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy(KArgs a, PArgs p) {
 #pragma unroll
         for (int j = 0; j < O; ++j) stt[SO - O + j] = tb[j];
         if (boot) {
-          const bool bt = valid && (db & LZ_DONE_TRUNCATED) && !(db & LZ_DONE_TERMINATED);
+          const bool bt = valid && is_truncation(db);
           if (__ballot(bt) != 0ull) {
             bf16x8 xs[KS], f[4];
             stack_frags<SO, KS>(stt, h, bt, xs);
@@ -1234,7 +1337,7 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy(KArgs a, PArgs p) {
 #pragma unroll
         for (int j = 0; j < O; ++j) st[SO - O + j] = nb[j];
       } else if (boot) {  // SB3: truncated (not terminated) -> rewards += gamma * V(terminal obs)
-        const bool bt = live && (df & LZ_DONE_TRUNCATED) && !(df & LZ_DONE_TERMINATED);
+        const bool bt = live && is_truncation(df);
         if (__ballot(bt) != 0ull) {  // wave-uniform branch
           float xt[O], vt[1];
           normalize<O>(ot, xt, norm, mu, sd, p.clip);
@@ -1281,25 +1384,19 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy(KArgs a, PArgs p) {
       normalize<O>(o, x, norm, mu, sd, p.clip);
       value_fwd<E, O, kPair>(s_blob, vf_net, x, live, lane, vl);
     }
-    if (live) {
-      p.last_val[i] = vl[0];
-#pragma unroll
-      for (int j = 0; j < O; ++j) p.obs_last[i * O + j] = o[j];
-      sys.store(a, i);
-      if (any_reset) sys.store_autoreset_extra(a, i);
-      if (a.count_steps) static_cast<int32_t*>(a.pl[Sys::kStepPlane])[i] = steps;
-    }
+    if (live) p.last_val[i] = vl[0];
+    tile_close(sys, a, p, i, live, steps, any_reset, o);
   }
-  if (kPair != kAttnLn && p.partials) {  // fixed-order butterfly over the wave: deterministic
+  if (kPair != kAttnLn && p.partials) {
     double* dst = p.partials + ((int64_t)blockIdx.x * W + wave) * (2 * O);
+    if constexpr (kRegMom) {
+      moments_store<O>(dst, mom_r, h, lane);
+    } else {  // the LDS accumulators of the env-owning lanes
 #pragma unroll
-    for (int j = 0; j < 2 * O; ++j) {
-      double v;
-      if constexpr (kRegMom) v = (j < O ? h == 0 : h == 1) ? mom_r[j < O ? j : j - O] : 0.0;
-      else v = owner ? mom[j] : 0.0;
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-      if (lane == 0) dst[j] = v;
+      for (int j = 0; j < 2 * O; ++j) {
+        const double v = wave_sum(owner ? mom[j] : 0.0);
+        if (lane == 0) dst[j] = v;
+      }
     }
   }
 }
@@ -1341,22 +1438,12 @@ __global__ __launch_bounds__(512) void k_rollout_policy_f32_split(KArgs a, PArgs
   const bool owner = h == 0;
   blob_to_lds(reinterpret_cast<f4v*>(s_blob), reinterpret_cast<const f4v*>(p.blob), kF32BlobBytes / 16,
               tid, 2 * T * 64, !blob_is(p.blob, kF32Tag, kI8 ? LZ_BLOB_MLP_I8X4 : LZ_BLOB_MLP_F32));
-  if (tid < O) {
-    s_norm[tid] = p.norm ? p.norm[tid] : 0.0;
-    s_norm[kPolMaxObs + tid] = p.norm ? sqrt(p.norm[O + tid] + p.eps) : 1.0;
-  }
-  const uint64_t tick = *a.tick_in;
-  if (blockIdx.x == 0 && tid == 0) {
-    *a.counter_next = 0;
-    *a.tick_out = tick + a.tick_adv;
-  }
+  const uint64_t tick = pol_prologue<O>(a, p, s_norm, tid);
   __syncthreads();
   const uint8_t* pi_net = s_blob;
   const uint8_t* vf_net = s_blob + kF32Net;
   const float* ttab = reinterpret_cast<const float*>(s_blob + kF32Tanh);
   const float* g_scale = reinterpret_cast<const float*>(s_blob + kF32LogStd) + 4;
-  const float* g_var2 = g_scale + 4;
-  const float* g_lscale = g_scale + 8;
   const bool norm = p.norm != nullptr;
   const double* mu = s_norm;
   const double* sd = s_norm + kPolMaxObs;
@@ -1375,17 +1462,10 @@ __global__ __launch_bounds__(512) void k_rollout_policy_f32_split(KArgs a, PArgs
     if (wave < T) {  // ---- actor
       Sys sys;
       sys.setup(a);
-      int32_t steps = 0;
+      int32_t steps;
       bool any_reset = false;
       float o[O];
-#pragma unroll
-      for (int j = 0; j < O; ++j) o[j] = 0.0f;
-      if (live) {
-        sys.load(a, i);
-        if (a.count_steps) steps = static_cast<const int32_t*>(a.pl[Sys::kStepPlane])[i];
-#pragma unroll
-        for (int j = 0; j < O; ++j) o[j] = p.obs_in[i * O + j];
-      }
+      tile_open(sys, a, p, i, live, steps, o);
       __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see k_rollout_policy
       for (int k = 0; k < a.K; ++k) {
         lds_barrier();  // M_k: the critic has read step k - 1's hand-over
@@ -1401,22 +1481,10 @@ __global__ __launch_bounds__(512) void k_rollout_policy_f32_split(KArgs a, PArgs
         mlp_f32<KS1, A, kI8>(pi_net, xs, lane, mean, ttab);
         float act_c[A];
         if (live) {
-          float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-          if (!det) {
-            if constexpr (A <= 2) normal2(a.seed, (uint64_t)(a.gid0 + i), tick + (uint64_t)k, z);
-            else normal4(a.seed, (uint64_t)(a.gid0 + i), tick + (uint64_t)k, z);
-          }
-          float lp = 0.0f;
+          float act[A];
+          p.logp[off] = policy_sample<A, true>(a, p, i, tick + (uint64_t)k, det, mean, g_scale, act, act_c);
 #pragma unroll
-          for (int j = 0; j < A; ++j) {
-            const float aj = det ? mean[j] : mean[j] + z[j] * g_scale[j];
-            const float d = aj - mean[j];
-            const float lpj = (-(d * d)) / g_var2[j] - g_lscale[j] - 0.91893853320467274f;
-            lp = j == 0 ? lpj : lp + lpj;
-            act_c[j] = clip(aj, p.act_lo, p.act_hi);
-            p.act[off * A + j] = aj;
-          }
-          p.logp[off] = lp;
+          for (int j = 0; j < A; ++j) p.act[off * A + j] = act[j];
         }
         float on[O], ot[O];
         float rew = 0.0f;
@@ -1446,13 +1514,7 @@ __global__ __launch_bounds__(512) void k_rollout_policy_f32_split(KArgs a, PArgs
         for (int j = 0; j < O; ++j) o[j] = on[j];
         lds_barrier();  // B_k: step k's hand-over is written
       }
-      if (live) {
-#pragma unroll
-        for (int j = 0; j < O; ++j) p.obs_last[i * O + j] = o[j];
-        sys.store(a, i);
-        if (any_reset) sys.store_autoreset_extra(a, i);
-        if (a.count_steps) static_cast<int32_t*>(a.pl[Sys::kStepPlane])[i] = steps;
-      }
+      tile_close(sys, a, p, i, live, steps, any_reset, o);
     } else {  // ---- critic
       float o[O], ot[O];
       float rew = 0.0f;
@@ -1474,7 +1536,7 @@ __global__ __launch_bounds__(512) void k_rollout_policy_f32_split(KArgs a, PArgs
       // step kk's truncation bootstrap (SB3: rewards += gamma * V(terminal obs)), reward out
       auto settle = [&](int kk) {
         if (boot) {
-          const bool bt = live && (df & LZ_DONE_TRUNCATED) && !(df & LZ_DONE_TERMINATED);
+          const bool bt = live && is_truncation(df);
           if (__ballot(bt) != 0ull) {
             float xt[O], vt[1];
             normalize<O>(ot, xt, norm, mu, sd, p.clip);
@@ -1503,16 +1565,8 @@ __global__ __launch_bounds__(512) void k_rollout_policy_f32_split(KArgs a, PArgs
       if (live) p.last_val[i] = vl[0];
     }
   }
-  if (wave < T && p.partials) {  // fixed-order butterfly over the wave, as k_rollout_policy
-    double* dst = p.partials + ((int64_t)blockIdx.x * T + wave) * (2 * O);
-#pragma unroll
-    for (int j = 0; j < 2 * O; ++j) {
-      double v = (j < O ? h == 0 : h == 1) ? mom_r[j < O ? j : j - O] : 0.0;
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-      if (lane == 0) dst[j] = v;
-    }
-  }
+  if (wave < T && p.partials)  // one partial per actor wave, as k_rollout_policy
+    moments_store<O>(p.partials + ((int64_t)blockIdx.x * T + wave) * (2 * O), mom_r, h, lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1561,8 +1615,6 @@ __global__ __launch_bounds__(W * 64) void k_policy_step_f32(KArgs a, PArgs p, PS
   const uint8_t* vf_net = s_blob + kF32Net;
   const float* ttab = reinterpret_cast<const float*>(s_blob + kF32Tanh);
   const float* g_scale = reinterpret_cast<const float*>(s_blob + kF32LogStd) + 4;
-  const float* g_var2 = g_scale + 4;
-  const float* g_lscale = g_scale + 8;
   const double* mu = s_norm;
   const double* sd = s_norm + kPolMaxObs;
   const bool det = (p.pflags & LZ_POLICY_DETERMINISTIC) != 0;
@@ -1581,7 +1633,7 @@ __global__ __launch_bounds__(W * 64) void k_policy_step_f32(KArgs a, PArgs p, PS
     if (boot && k > 0) {
       const int64_t po = (int64_t)(k - 1) * a.n + i;
       const uint8_t d = live ? a.done[po] : (uint8_t)0;
-      const bool bt = live && (d & LZ_DONE_TRUNCATED) && !(d & LZ_DONE_TERMINATED);
+      const bool bt = live && is_truncation(d);
       if (__ballot(bt) != 0ull) {  // wave-uniform
         float ot[O], xt[O], vt[1];
 #pragma unroll
@@ -1602,11 +1654,8 @@ __global__ __launch_bounds__(W * 64) void k_policy_step_f32(KArgs a, PArgs p, PS
       if (live) p.last_val[i] = vl[0];
       continue;
     }
-    int32_t steps = 0;
-    if (live) {
-      sys.load(a, i);
-      if (a.count_steps) steps = static_cast<const int32_t*>(a.pl[Sys::kStepPlane])[i];
-    }
+    int32_t steps;
+    state_open(sys, a, i, live, steps);
     const int64_t off = (int64_t)k * a.n + i;
     if (live) {
 #pragma unroll
@@ -1622,17 +1671,13 @@ __global__ __launch_bounds__(W * 64) void k_policy_step_f32(KArgs a, PArgs p, PS
     }
     float act_c[A];
     if (live) {
-      float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (!det) {
-        if constexpr (A <= 2) normal2(a.seed, (uint64_t)(a.gid0 + i), tick, z);
-        else normal4(a.seed, (uint64_t)(a.gid0 + i), tick, z);
-      }
+      float z[4];  // policy_sample's loop in place (see there)
+      policy_draw<A>(a, i, tick, det, z);
       float lp = 0.0f;
 #pragma unroll
       for (int j = 0; j < A; ++j) {
-        const float aj = det ? mean[j] : mean[j] + z[j] * g_scale[j];
-        const float dd = aj - mean[j];
-        const float lpj = (-(dd * dd)) / g_var2[j] - g_lscale[j] - 0.91893853320467274f;
+        const float aj = normal_rsample(mean[j], z[j], g_scale, j, det);
+        const float lpj = normal_logp(aj, mean[j], g_scale, j);
         lp = j == 0 ? lpj : lp + lpj;
         act_c[j] = clip(aj, p.act_lo, p.act_hi);
         p.act[off * A + j] = aj;
@@ -1648,16 +1693,12 @@ __global__ __launch_bounds__(W * 64) void k_policy_step_f32(KArgs a, PArgs p, PS
     if (live) {
       rew_buf[off] = rew;
       a.done[off] = df;
-#pragma unroll
-      for (int j = 0; j < O; ++j) p.obs_last[i * O + j] = on[j];
       if (df) {
 #pragma unroll
         for (int j = 0; j < O; ++j) s.term[i * O + j] = ot[j];
       }
-      sys.store(a, i);
-      if (did_reset) sys.store_autoreset_extra(a, i);
-      if (a.count_steps) static_cast<int32_t*>(a.pl[Sys::kStepPlane])[i] = steps;
     }
+    tile_close(sys, a, p, i, live, steps, did_reset, on);
     // 3. the tile's float64 moments of the raw obs VecNormalize updates obs_rms with:
     // half 0 sums, half 1 squares, a 32-lane butterfly within each half
     if (s.tiles) {
@@ -2129,14 +2170,100 @@ __device__ __forceinline__ void dma16_keep(const void* g, uint32_t m0) {
                : "memory");
 }
 
+// One net (kAFNet bytes at g) into the LDS net slot s_net: this wave's share of the 100
+// 1-KiB pieces.  The caller waits (vmcnt(0), then a barrier) before the slot is read.
+template <int W>
+__device__ __forceinline__ void net_dma(const uint8_t* g, const uint8_t* s_net, int wave, int lane) {
+  const uint32_t m0_net = __builtin_amdgcn_readfirstlane(
+      (uint32_t)(uintptr_t)(las_p)(const_cast<uint8_t*>(s_net)));
+  const int wv = __builtin_amdgcn_readfirstlane(wave);  // M0 takes a wave-uniform SGPR
+  for (int c = wv; c < kAFNet / 1024; c += W)
+    dma16_keep(g + c * 1024 + lane * 16, (uint32_t)__builtin_amdgcn_readfirstlane(m0_net + 1024u * c));
+}
+
+// The float32 attention kernels' fc1 inputs and VecFrameStack (S frames of O dims), seen
+// from one lane: lane group G = lane >> 4 of env column col = lane & 15.  The frame stack
+// lives distributed like the fc1 inputs it feeds -- lane group G holds entries 4s + G
+// (s < KS) of its env's stack, 1/4 of it.  The policy's input (the deferred zeroing
+// applied) / the stacked terminal observation of a pending bootstrap ([older frames,
+// terminal frame]) are then per-lane selects.
+template <int O, int S>
+struct AttnStack {
+  static constexpr int SO = S * O, KS = (SO + 3) / 4;
+  static constexpr int SZ = SO - O;  // the stack's older frames
+  int G, col;
+
+  // this lane group's fc1 inputs: input 4s + G of the stacked / normalised input src
+  __device__ __forceinline__ void inputs(const float* src, float* xs) const {
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      float v = 0.0f;
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        if (4 * s + g < SO) v = G == g ? src[4 * s + g < SO ? 4 * s + g : 0] : v;
+      xs[s] = v;
+    }
+  }
+  // this lane's entries of row i of a [N][SO] stack buffer, from / to global memory
+  __device__ __forceinline__ void load(const float* buf, int64_t i, bool valid, float* stv) const {
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+      stv[s] = (valid && 4 * s + G < SO) ? buf[i * SO + (4 * s + G < SO ? 4 * s + G : 0)] : 0.0f;
+  }
+  __device__ __forceinline__ void store(float* buf, int64_t row, const float* xs) const {
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+      if (4 * s + G < SO) buf[row * SO + 4 * s + G] = xs[s];
+  }
+  // the stack with a done env's older frames zeroed (z): the zeroing is deferred until the
+  // bootstrap of the step has read [stv[0 .. SZ), terminal frame]; xs may be stv itself
+  __device__ __forceinline__ void cur_stack(const float* stv, bool z, float* xs) const {
+#pragma unroll
+    for (int s = 0; s < KS; ++s) xs[s] = (z && 4 * s + G < SZ) ? 0.0f : stv[s];
+  }
+  __device__ __forceinline__ float frame_at(const float* f, int q) const {  // f[q], lane-varying q in [0, O)
+    float v = 0.0f;
+#pragma unroll
+    for (int j = 0; j < O; ++j) v = q == j ? f[j] : v;
+    return v;
+  }
+  // SB3's stacked terminal observation: [rolled older frames, terminal frame tf]
+  __device__ __forceinline__ void term_stack(const float* stv, const float* tf, float* xs) const {
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const int q = 4 * s + G;
+      xs[s] = q < SZ ? stv[s] : (q < SO ? frame_at(tf, q - SZ) : 0.0f);
+    }
+  }
+  // VecFrameStack roll (SB3 StackedObservations.update): entry q takes q + O, the new
+  // frame nf lands in the last O.  Entry q + O lives in lane group (G + O) & 3, slot
+  // s + O / 4 (+1 when G + O % 4 wraps): one lane permute per slot pair.
+  __device__ __forceinline__ void roll_stack(float* stv, const float* nf) const {
+    const int src = (((G + O) & 3) << 4) | col;
+    const bool carry = G + (O & 3) >= 4;
+    float nst[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      constexpr int D = O / 4;
+      const float va = __shfl(s + D < KS ? stv[s + D < KS ? s + D : 0] : 0.0f, src, 64);
+      const float vb = __shfl(s + D + 1 < KS ? stv[s + D + 1 < KS ? s + D + 1 : 0] : 0.0f, src, 64);
+      const int q = 4 * s + G;
+      const float v = carry ? vb : va;
+      nst[s] = q < SZ ? v : (q < SO ? frame_at(nf, q - SZ) : 0.0f);
+    }
+#pragma unroll
+    for (int s = 0; s < KS; ++s) stv[s] = nst[s];
+  }
+};
+
 template <class Sys, bool kLn, int S, int W, bool kI8 = false>
 __global__ __launch_bounds__(W * 64) void k_rollout_policy_attn_f32(KArgs a, PArgs p) {
   constexpr int E = 16;
   constexpr int O = Sys::O, A = Sys::A;
-  constexpr int SO = S * O, KS = (SO + 3) / 4;
+  using Stack = AttnStack<O, S>;
+  constexpr int SO = Stack::SO, KS = Stack::KS;
   static_assert(kLn || S == 1, "frame stacking is the LayerNorm variant's");
   static_assert(SO <= kAFMaxIn && O <= kPolMaxObs && A <= kPolMaxAct, "policy tile shape");
-  constexpr int SZ = SO - O;  // the stack's older frames
   __shared__ __attribute__((aligned(16))) uint8_t s_lds[kAFLdsBytes];
   __shared__ double s_norm[2 * kPolMaxObs];
   __shared__ __attribute__((aligned(16))) int16_t s_psh[kI8 ? kAttFeat : 8];  // kI8: post_fc row shifts
@@ -2157,32 +2284,15 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy_attn_f32(KArgs a, PAr
         reinterpret_cast<f4v*>(s_psh)[tid] = reinterpret_cast<const f4v*>(p.blob + kAFPi + kAXPostSh)[tid];
     }
   }
-  if (tid < O) {
-    s_norm[tid] = p.norm ? p.norm[tid] : 0.0;
-    s_norm[kPolMaxObs + tid] = p.norm ? sqrt(p.norm[O + tid] + p.eps) : 1.0;
-  }
-  const uint64_t tick = *a.tick_in;
-  if (blockIdx.x == 0 && tid == 0) {
-    *a.counter_next = 0;
-    *a.tick_out = tick + a.tick_adv;
-  }
+  const uint64_t tick = pol_prologue<O>(a, p, s_norm, tid);
   __syncthreads();
   const uint8_t* s_ext = s_lds;
   const float* cst = reinterpret_cast<const float*>(s_lds + kAFExt);
-  const float* g_scale = cst + 4;
-  const float* g_var2 = cst + 8;
-  const float* g_lscale = cst + 12;
+  const float* g_scale = cst + 4;  // policy_sample's Normal constants
   const float* ttab = cst + 16;
   const uint8_t* s_net = s_lds + kAFExt + kAFConst;
-  const uint32_t m0_net = __builtin_amdgcn_readfirstlane(
-      (uint32_t)(uintptr_t)(las_p)(const_cast<uint8_t*>(s_net)));
   const uint8_t* g_pi = p.blob + kAFPi;
   const uint8_t* g_vf = p.blob + kAFVf;
-  auto net_dma = [&](const uint8_t* g) {  // this wave's share of the 100 1-KiB pieces
-    const int wv = __builtin_amdgcn_readfirstlane(wave);  // M0 takes a wave-uniform SGPR
-    for (int c = wv; c < kAFNet / 1024; c += W)
-      dma16_keep(g + c * 1024 + lane * 16, (uint32_t)__builtin_amdgcn_readfirstlane(m0_net + 1024u * c));
-  };
   const bool norm = p.norm != nullptr;
   const double* mu = s_norm;
   const double* sd = s_norm + kPolMaxObs;
@@ -2199,64 +2309,14 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy_attn_f32(KArgs a, PAr
   const int64_t ntiles = (a.n + E - 1) / E;
   const int64_t per_round = (int64_t)gridDim.x * W;
   const int64_t rounds = (ntiles + per_round - 1) / per_round;
-  // this lane group's fc1 inputs: input 4s + G of the stacked / normalised input
-  auto inputs = [&](const float* src, float* xs) {
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      float v = 0.0f;
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        if (4 * s + g < SO) v = G == g ? src[4 * s + g < SO ? 4 * s + g : 0] : v;
-      xs[s] = v;
-    }
-  };
-  // kLn: the frame stack lives distributed like the fc1 inputs it feeds -- lane group G
-  // holds entries 4s + G (s < KS) of its env's stack, 1/4 of it.  The policy's input
-  // (the deferred zeroing applied) / the stacked terminal observation of a pending
-  // bootstrap ([older frames, terminal frame]) are then per-lane selects.
-  auto cur_stack = [&](const float* stv, bool z, float* xs) {
-#pragma unroll
-    for (int s = 0; s < KS; ++s) xs[s] = (z && 4 * s + G < SZ) ? 0.0f : stv[s];
-  };
-  auto frame_at = [&](const float* f, int q) {  // f[q] for a lane-varying q in [0, O)
-    float v = 0.0f;
-#pragma unroll
-    for (int j = 0; j < O; ++j) v = q == j ? f[j] : v;
-    return v;
-  };
-  auto term_stack = [&](const float* stv, const float* tf, float* xs) {
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int q = 4 * s + G;
-      xs[s] = q < SZ ? stv[s] : (q < SO ? frame_at(tf, q - SZ) : 0.0f);
-    }
-  };
-  // VecFrameStack roll (SB3 StackedObservations.update): entry q takes q + O, the new
-  // frame lands in the last O.  Entry q + O lives in lane group (G + O) & 3, slot
-  // s + O / 4 (+1 when G + O % 4 wraps): one lane permute per slot pair.
-  auto roll_stack = [&](float* stv, const float* nf) {
-    const int src = (((G + O) & 3) << 4) | col;
-    const bool carry = G + (O & 3) >= 4;
-    float nst[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      constexpr int D = O / 4;
-      const float va = __shfl(s + D < KS ? stv[s + D < KS ? s + D : 0] : 0.0f, src, 64);
-      const float vb = __shfl(s + D + 1 < KS ? stv[s + D + 1 < KS ? s + D + 1 : 0] : 0.0f, src, 64);
-      const int q = 4 * s + G;
-      const float v = carry ? vb : va;
-      nst[s] = q < SZ ? v : (q < SO ? frame_at(nf, q - SZ) : 0.0f);
-    }
-#pragma unroll
-    for (int s = 0; s < KS; ++s) stv[s] = nst[s];
-  };
+  const Stack stk = {G, col};
   for (int64_t rd = 0; rd < rounds; ++rd) {
     const int64_t tile = (rd * gridDim.x + blockIdx.x) * W + wave;
     const bool active = tile < ntiles;  // wave-uniform; inactive waves still swap the slot
     const int64_t i = tile * E + col;
     const bool valid = active && i < a.n;  // all four lanes of the env compute it
     const bool own = valid && G == 0;      // ... lane group 0 stores it
-    int32_t steps = 0;
+    int32_t steps;
     bool any_reset = false;
     // pt: the raw terminal obs of a pending bootstrap.  kLn: st is the rolled stack with
     // the zeroing of a done env's older frames deferred (zf) until the bootstrap of the
@@ -2264,18 +2324,9 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy_attn_f32(KArgs a, PAr
     float o[O], st[kLn ? KS : 1], pt[O];
     bool zf = false;
 #pragma unroll
-    for (int j = 0; j < O; ++j) o[j] = pt[j] = 0.0f;
-    if (valid) {
-      sys.load(a, i);
-      if (a.count_steps) steps = static_cast<const int32_t*>(a.pl[Sys::kStepPlane])[i];
-#pragma unroll
-      for (int j = 0; j < O; ++j) o[j] = p.obs_in[i * O + j];
-    }
-    if constexpr (kLn) {
-#pragma unroll
-      for (int s = 0; s < KS; ++s)
-        st[s] = (valid && 4 * s + G < SO) ? p.stack_in[i * SO + (4 * s + G < SO ? 4 * s + G : 0)] : 0.0f;
-    }
+    for (int j = 0; j < O; ++j) pt[j] = 0.0f;
+    tile_open(sys, a, p, i, valid, steps, o);
+    if constexpr (kLn) stk.load(p.stack_in, i, valid, st);
     bool pend = false;  // this env's step truncated: its bootstrap value comes next step
     float prew = 0.0f;  // ... and its reward before the bootstrap
     __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -2283,7 +2334,7 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy_attn_f32(KArgs a, PAr
       const int64_t off = (int64_t)k * a.n + i;
       // [1] pi into the slot, meanwhile the features of this step's input
       __syncthreads();
-      net_dma(g_pi);
+      net_dma<W>(g_pi, s_net, wave, lane);
       const bool pb = pend;
       const bool any_pb = __ballot(pb) != 0ull;
       f32x4 F[4], Ft[4];
@@ -2291,12 +2342,8 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy_attn_f32(KArgs a, PAr
       if (active) {
         float xs[KS];
         if constexpr (kLn) {
-          cur_stack(st, zf, xs);
-          if (valid) {  // every lane group stores its entries of the stacked row
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-              if (4 * s + G < SO) obs_buf[off * SO + 4 * s + G] = xs[s];
-          }
+          stk.cur_stack(st, zf, xs);
+          if (valid) stk.store(obs_buf, off, xs);  // every lane group its entries of the stacked row
         } else {
           float x[O];
           normalize<O>(o, x, norm, mu, sd, p.clip);
@@ -2304,7 +2351,7 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy_attn_f32(KArgs a, PAr
 #pragma unroll
             for (int j = 0; j < O; ++j) obs_buf[off * O + j] = x[j];
           }
-          inputs(x, xs);
+          stk.inputs(x, xs);
         }
         attn16_extract<KS, kLn, kI8>(s_ext, xs, lane, F, s_psh);
         if constexpr (kI8) FI = i8x_feat(F);
@@ -2319,54 +2366,43 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy_attn_f32(KArgs a, PAr
         float mean[A];
         attn16_net_sel<A, kI8>(s_net, F, FI, lane, mean, ttab);
         if (valid) {
-          float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-          if (!det) {
-            if constexpr (A <= 2) normal2(a.seed, (uint64_t)(a.gid0 + i), tick + (uint64_t)k, z);
-            else normal4(a.seed, (uint64_t)(a.gid0 + i), tick + (uint64_t)k, z);
-          }
-          float lp = 0.0f;
+          float act[A];
+          const float lp = policy_sample<A, true>(a, p, i, tick + (uint64_t)k, det, mean, g_scale, act, act_c);
+          if (own) {
 #pragma unroll
-          for (int j = 0; j < A; ++j) {
-            const float aj = det ? mean[j] : mean[j] + z[j] * g_scale[j];
-            const float dd = aj - mean[j];
-            const float lpj = (-(dd * dd)) / g_var2[j] - g_lscale[j] - 0.91893853320467274f;
-            lp = j == 0 ? lpj : lp + lpj;
-            act_c[j] = clip(aj, p.act_lo, p.act_hi);
-            if (own) p.act[off * A + j] = aj;
+            for (int j = 0; j < A; ++j) p.act[off * A + j] = act[j];
+            p.logp[off] = lp;
           }
-          if (own) p.logp[off] = lp;
         }
       }
       // [3] vf into the slot while the previous step's pending terminal input is
       //     extracted and the env steps (which overwrites pt)
       __syncthreads();
-      net_dma(g_vf);
+      net_dma<W>(g_vf, s_net, wave, lane);
       float rew = 0.0f;
       bool pn = false;
       if (active) {
         if (any_pb) {
           float xt[KS];
           if constexpr (kLn) {
-            term_stack(st, pt, xt);
+            stk.term_stack(st, pt, xt);
           } else {
             float x[O];
             normalize<O>(pt, x, norm, mu, sd, p.clip);
-            inputs(x, xt);
+            stk.inputs(x, xt);
           }
           attn16_extract<KS, kLn, kI8>(s_ext, xt, lane, Ft, s_psh);
           if constexpr (kI8) FIt = i8x_feat(Ft);
         }
-        if constexpr (kLn) {  // the deferred zeroing, now that the bootstrap has its input
-#pragma unroll
-          for (int s = 0; s < KS; ++s) st[s] = (zf && 4 * s + G < SZ) ? 0.0f : st[s];
-        }
+        // the deferred zeroing, now that the bootstrap has its input
+        if constexpr (kLn) stk.cur_stack(st, zf, st);
         float on[O], ot[O];
         bool did_reset;
         const uint8_t df = step_body<Sys, float, true, true>(sys, steps, a, i, valid, act_c,
                                                              tick + (uint64_t)k, k, on, rew,
                                                              did_reset, ot, G == 0);
         any_reset = any_reset || did_reset;
-        pn = boot && valid && (df & LZ_DONE_TRUNCATED) && !(df & LZ_DONE_TERMINATED);
+        pn = boot && valid && is_truncation(df);
         if (pn) {
 #pragma unroll
           for (int j = 0; j < O; ++j) pt[j] = ot[j];
@@ -2375,7 +2411,7 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy_attn_f32(KArgs a, PAr
           // VecFrameStack (SB3 StackedObservations.update): roll by O, the new frame last;
           // a done env's older frames become zeros (deferred: zf) -- its stacked terminal
           // observation is [rolled older frames, terminal frame]
-          roll_stack(st, on);
+          stk.roll_stack(st, on);
           zf = df != 0;
         } else {
           if (p.partials && valid && G < 2) {
@@ -2417,24 +2453,24 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy_attn_f32(KArgs a, PAr
       I8Feat FI;
       float xs[KS];
       if constexpr (kLn) {
-        cur_stack(st, zf, xs);
+        stk.cur_stack(st, zf, xs);
       } else {
         float x[O];
         normalize<O>(o, x, norm, mu, sd, p.clip);
-        inputs(x, xs);
+        stk.inputs(x, xs);
       }
       attn16_extract<KS, kLn, kI8>(s_ext, xs, lane, F, s_psh);
-        if constexpr (kI8) FI = i8x_feat(F);
+      if constexpr (kI8) FI = i8x_feat(F);
       float vl[1];
       attn16_net_sel<1, kI8>(s_net, F, FI, lane, vl, ttab);
       if (any_pb) {
         float xt[KS];
         if constexpr (kLn) {
-          term_stack(st, pt, xt);
+          stk.term_stack(st, pt, xt);
         } else {
           float x[O];
           normalize<O>(pt, x, norm, mu, sd, p.clip);
-          inputs(x, xt);
+          stk.inputs(x, xt);
         }
         attn16_extract<KS, kLn, kI8>(s_ext, xt, lane, F, s_psh);
         if constexpr (kI8) FI = i8x_feat(F);
@@ -2442,33 +2478,15 @@ __global__ __launch_bounds__(W * 64) void k_rollout_policy_attn_f32(KArgs a, PAr
         attn16_net_sel<1, kI8>(s_net, F, FI, lane, vt, ttab);
         if (own && pb) rew_buf[(int64_t)(a.K - 1) * a.n + i] = prew + gamma * vt[0];
       }
-      if (own) {
-        p.last_val[i] = vl[0];
-#pragma unroll
-        for (int j = 0; j < O; ++j) p.obs_last[i * O + j] = o[j];
-        sys.store(a, i);
-        if (any_reset) sys.store_autoreset_extra(a, i);
-        if (a.count_steps) static_cast<int32_t*>(a.pl[Sys::kStepPlane])[i] = steps;
-      }
+      if (own) p.last_val[i] = vl[0];
+      tile_close(sys, a, p, i, own, steps, any_reset, o);
       if constexpr (kLn) {
-        if (valid) {
-#pragma unroll
-          for (int s = 0; s < KS; ++s)
-            if (4 * s + G < SO) p.stack_out[i * SO + 4 * s + G] = xs[s];
-        }
+        if (valid) stk.store(p.stack_out, i, xs);
       }
     }
   }
-  if (!kLn && p.partials) {  // fixed-order butterfly over the wave: deterministic
-    double* dst = p.partials + ((int64_t)blockIdx.x * W + wave) * (2 * O);
-#pragma unroll
-    for (int j = 0; j < 2 * O; ++j) {
-      double v = (j < O ? G == 0 : G == 1) ? mom_r[j < O ? j : j - O] : 0.0;
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-      if (lane == 0) dst[j] = v;
-    }
-  }
+  if (!kLn && p.partials)
+    moments_store<O>(p.partials + ((int64_t)blockIdx.x * W + wave) * (2 * O), mom_r, G, lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2615,15 +2633,7 @@ __global__ __launch_bounds__(W * 64) void k_evaluate_policy_f32(KArgs a, PArgs p
               W * 64, bad);
   blob_to_lds(reinterpret_cast<f4v*>(s_cst), reinterpret_cast<const f4v*>(p.blob + kF32LogStd), kCst / 16,
               tid, W * 64, bad);
-  if (tid < O) {  // VecNormalize: mean and sqrt(var + eps) per obs dim
-    s_norm[tid] = p.norm ? p.norm[tid] : 0.0;
-    s_norm[kPolMaxObs + tid] = p.norm ? sqrt(p.norm[O + tid] + p.eps) : 1.0;
-  }
-  const uint64_t tick = *a.tick_in;
-  if (blockIdx.x == 0 && tid == 0) {
-    *a.counter_next = 0;
-    *a.tick_out = tick + a.tick_adv;
-  }
+  const uint64_t tick = pol_prologue<O>(a, p, s_norm, tid);
   __syncthreads();
   const float* g_scale = reinterpret_cast<const float*>(s_cst) + 4;
   const float* ttab = reinterpret_cast<const float*>(s_cst + 64);
@@ -2638,20 +2648,13 @@ __global__ __launch_bounds__(W * 64) void k_evaluate_policy_f32(KArgs a, PArgs p
   for (int64_t tile = (int64_t)blockIdx.x * W + wave; tile < ntiles; tile += (int64_t)gridDim.x * W) {
     const int64_t i = tile * E + slot;
     const bool live = owner && i < a.n;
-    int32_t steps = 0;
+    int32_t steps;
     bool any_reset = false;
     double q[4][4];  // this tile's accumulators: zeroed per grid-stride tile
     EvalCount c;
     eval_zero<4>(q, c);
     float o[O];
-#pragma unroll
-    for (int j = 0; j < O; ++j) o[j] = 0.0f;
-    if (live) {
-      sys.load(a, i);
-      if (a.count_steps) steps = static_cast<const int32_t*>(a.pl[Sys::kStepPlane])[i];
-#pragma unroll
-      for (int j = 0; j < O; ++j) o[j] = p.obs_in[i * O + j];
-    }
+    tile_open(sys, a, p, i, live, steps, o);
     for (int k = 0; k < a.K; ++k) {
       float x[O];
       normalize<O>(o, x, norm, mu, sd, p.clip);
@@ -2661,16 +2664,8 @@ __global__ __launch_bounds__(W * 64) void k_evaluate_policy_f32(KArgs a, PArgs p
       mlp_f32<(O + 1) / 2, A>(s_net, xs, lane, mean, ttab);
       float act_c[A];
       if (live) {
-        float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (!det) {
-          if constexpr (A <= 2) normal2(a.seed, (uint64_t)(a.gid0 + i), tick + (uint64_t)k, z);
-          else normal4(a.seed, (uint64_t)(a.gid0 + i), tick + (uint64_t)k, z);
-        }
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-          const float aj = det ? mean[j] : mean[j] + z[j] * g_scale[j];  // Normal.rsample
-          act_c[j] = clip(aj, p.act_lo, p.act_hi);
-        }
+        float act[A];
+        policy_sample<A, false>(a, p, i, tick + (uint64_t)k, det, mean, g_scale, act, act_c);
       }
       float on[O], ot[O];
       float rew = 0.0f;
@@ -2682,14 +2677,8 @@ __global__ __launch_bounds__(W * 64) void k_evaluate_policy_f32(KArgs a, PArgs p
 #pragma unroll
       for (int j = 0; j < O; ++j) o[j] = on[j];
     }
-    if (live) {
-#pragma unroll
-      for (int j = 0; j < O; ++j) p.obs_last[i * O + j] = o[j];
-      sys.store(a, i);
-      if (any_reset) sys.store_autoreset_extra(a, i);
-      if (a.count_steps) static_cast<int32_t*>(a.pl[Sys::kStepPlane])[i] = steps;
-      eval_store<4>(ev.stats, a.n, i, q, c, 0, true, bad);
-    }
+    tile_close(sys, a, p, i, live, steps, any_reset, o);
+    if (live) eval_store<4>(ev.stats, a.n, i, q, c, 0, true, bad);
   }
 }
 
@@ -2703,10 +2692,10 @@ template <class Sys, bool kLn, int S, int W>
 __global__ __launch_bounds__(W * 64) void k_evaluate_policy_attn_f32(KArgs a, PArgs p, EArgs ev) {
   constexpr int E = 16;
   constexpr int O = Sys::O, A = Sys::A, ED = O / 2;
-  constexpr int SO = S * O, KS = (SO + 3) / 4;
+  using Stack = AttnStack<O, S>;
+  constexpr int SO = Stack::SO, KS = Stack::KS;
   static_assert(kLn || S == 1, "frame stacking is the LayerNorm variant's");
   static_assert(SO <= kAFMaxIn && O <= kPolMaxObs && A <= kPolMaxAct && ED <= 4, "policy tile shape");
-  constexpr int SZ = SO - O;  // the stack's older frames
   __shared__ __attribute__((aligned(16))) uint8_t s_lds[kAFLdsBytes];
   __shared__ double s_norm[2 * kPolMaxObs];
   const int tid = (int)threadIdx.x;
@@ -2716,29 +2705,14 @@ __global__ __launch_bounds__(W * 64) void k_evaluate_policy_attn_f32(KArgs a, PA
               bad);
   blob_to_lds(reinterpret_cast<f4v*>(s_lds + kAFExt), reinterpret_cast<const f4v*>(p.blob + kAFLogStd),
               kAFConst / 16, tid, W * 64, bad);
-  if (tid < O) {
-    s_norm[tid] = p.norm ? p.norm[tid] : 0.0;
-    s_norm[kPolMaxObs + tid] = p.norm ? sqrt(p.norm[O + tid] + p.eps) : 1.0;
-  }
-  const uint64_t tick = *a.tick_in;
-  if (blockIdx.x == 0 && tid == 0) {
-    *a.counter_next = 0;
-    *a.tick_out = tick + a.tick_adv;
-  }
+  const uint64_t tick = pol_prologue<O>(a, p, s_norm, tid);
   const uint8_t* s_ext = s_lds;
   const float* cst = reinterpret_cast<const float*>(s_lds + kAFExt);
   const float* g_scale = cst + 4;
   const float* ttab = cst + 16;
   const uint8_t* s_net = s_lds + kAFExt + kAFConst;
-  {  // the pi net into the slot: this wave's share of the 100 1-KiB pieces
-    const uint32_t m0_net = __builtin_amdgcn_readfirstlane(
-        (uint32_t)(uintptr_t)(las_p)(const_cast<uint8_t*>(s_net)));
-    const uint8_t* g_pi = p.blob + kAFPi;
-    const int wv = __builtin_amdgcn_readfirstlane(wave);  // M0 takes a wave-uniform SGPR
-    for (int c = wv; c < kAFNet / 1024; c += W)
-      dma16_keep(g_pi + c * 1024 + lane * 16, (uint32_t)__builtin_amdgcn_readfirstlane(m0_net + 1024u * c));
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // this wave's DMA pieces have landed
-  }
+  net_dma<W>(p.blob + kAFPi, s_net, wave, lane);  // the pi net into the slot, once
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // this wave's DMA pieces have landed
   __syncthreads();
   const bool norm = p.norm != nullptr;
   const double* mu = s_norm;
@@ -2748,56 +2722,22 @@ __global__ __launch_bounds__(W * 64) void k_evaluate_policy_attn_f32(KArgs a, PA
   Sys sys;
   sys.setup(a);
   const int64_t ntiles = (a.n + E - 1) / E;
-  // this lane group's fc1 inputs: input 4s + G of the normalised input
-  auto inputs = [&](const float* src, float* xs) {
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      float v = 0.0f;
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        if (4 * s + g < SO) v = G == g ? src[4 * s + g < SO ? 4 * s + g : 0] : v;
-      xs[s] = v;
-    }
-  };
-  // kLn: lane group G holds entries 4s + G (s < KS) of its env's stack (k_rollout_policy_
-  // attn_f32's layout and roll)
-  auto cur_stack = [&](const float* stv, bool z, float* xs) {
-#pragma unroll
-    for (int s = 0; s < KS; ++s) xs[s] = (z && 4 * s + G < SZ) ? 0.0f : stv[s];
-  };
-  auto frame_at = [&](const float* f, int qi) {  // f[qi] for a lane-varying qi in [0, O)
-    float v = 0.0f;
-#pragma unroll
-    for (int j = 0; j < O; ++j) v = qi == j ? f[j] : v;
-    return v;
-  };
-  auto roll_stack = [&](float* stv, const float* nf) {
-    const int src = (((G + O) & 3) << 4) | col;
-    const bool carry = G + (O & 3) >= 4;
-    float nst[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      constexpr int D = O / 4;
-      const float va = __shfl(s + D < KS ? stv[s + D < KS ? s + D : 0] : 0.0f, src, 64);
-      const float vb = __shfl(s + D + 1 < KS ? stv[s + D + 1 < KS ? s + D + 1 : 0] : 0.0f, src, 64);
-      const int qi = 4 * s + G;
-      const float v = carry ? vb : va;
-      nst[s] = qi < SZ ? v : (qi < SO ? frame_at(nf, qi - SZ) : 0.0f);
-    }
-#pragma unroll
-    for (int s = 0; s < KS; ++s) stv[s] = nst[s];
-  };
+  const Stack stk = {G, col};
   for (int64_t tile = (int64_t)blockIdx.x * W + wave; tile < ntiles; tile += (int64_t)gridDim.x * W) {
     const int64_t i = tile * E + col;
     const bool valid = i < a.n;        // all four lanes of the env compute it
     const bool own = valid && G == 0;  // ... lane group 0 stores it
-    int32_t steps = 0;
+    int32_t steps;
     bool any_reset = false;
     double q[1][4];  // lane group G's part of this tile's accumulators, zeroed per tile
     EvalCount c;
     eval_zero<1>(q, c);
     float o[O], st[kLn ? KS : 1];
     bool zf = false;
+    // tile_open written out: called, the HR instance of this kernel measured 0.27 % slower
+    // (five alternating rounds against the previous code, its spread 0.22 %); with this
+    // block in place and every other shared step called, -0.02 %
+    steps = 0;
 #pragma unroll
     for (int j = 0; j < O; ++j) o[j] = 0.0f;
     if (valid) {
@@ -2806,20 +2746,16 @@ __global__ __launch_bounds__(W * 64) void k_evaluate_policy_attn_f32(KArgs a, PA
 #pragma unroll
       for (int j = 0; j < O; ++j) o[j] = p.obs_in[i * O + j];
     }
-    if constexpr (kLn) {
-#pragma unroll
-      for (int s = 0; s < KS; ++s)
-        st[s] = (valid && 4 * s + G < SO) ? p.stack_in[i * SO + (4 * s + G < SO ? 4 * s + G : 0)] : 0.0f;
-    }
+    if constexpr (kLn) stk.load(p.stack_in, i, valid, st);
     for (int k = 0; k < a.K; ++k) {
       f32x4 F[4];
       float xs[KS];
       if constexpr (kLn) {
-        cur_stack(st, zf, xs);
+        stk.cur_stack(st, zf, xs);
       } else {
         float x[O];
         normalize<O>(o, x, norm, mu, sd, p.clip);
-        inputs(x, xs);
+        stk.inputs(x, xs);
       }
       attn16_extract<KS, kLn>(s_ext, xs, lane, F);
       float mean[A];
@@ -2828,21 +2764,11 @@ __global__ __launch_bounds__(W * 64) void k_evaluate_policy_attn_f32(KArgs a, PA
 #pragma unroll
       for (int j = 0; j < A; ++j) act_c[j] = 0.0f;
       if (valid) {  // every lane of the env: the same Philox draw
-        float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (!det) {
-          if constexpr (A <= 2) normal2(a.seed, (uint64_t)(a.gid0 + i), tick + (uint64_t)k, z);
-          else normal4(a.seed, (uint64_t)(a.gid0 + i), tick + (uint64_t)k, z);
-        }
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-          const float aj = det ? mean[j] : mean[j] + z[j] * g_scale[j];
-          act_c[j] = clip(aj, p.act_lo, p.act_hi);
-        }
+        float act[A];
+        policy_sample<A, false>(a, p, i, tick + (uint64_t)k, det, mean, g_scale, act, act_c);
       }
-      if constexpr (kLn) {  // the deferred zeroing of a done env's older frames
-#pragma unroll
-        for (int s = 0; s < KS; ++s) st[s] = (zf && 4 * s + G < SZ) ? 0.0f : st[s];
-      }
+      // the deferred zeroing of a done env's older frames
+      if constexpr (kLn) stk.cur_stack(st, zf, st);
       float on[O], ot[O];
       float rew = 0.0f;
       bool did_reset;
@@ -2852,27 +2778,19 @@ __global__ __launch_bounds__(W * 64) void k_evaluate_policy_attn_f32(KArgs a, PA
       any_reset = any_reset || did_reset;
       if (valid) eval_step<1, ED>(q, c, G, ot, rew, df, k, autoreset, ev.skip, ev.max_episodes);
       if constexpr (kLn) {
-        roll_stack(st, on);
+        stk.roll_stack(st, on);
         zf = df != 0;
       }
 #pragma unroll
       for (int j = 0; j < O; ++j) o[j] = on[j];
     }
-    if (own) {
-#pragma unroll
-      for (int j = 0; j < O; ++j) p.obs_last[i * O + j] = o[j];
-      sys.store(a, i);
-      if (any_reset) sys.store_autoreset_extra(a, i);
-      if (a.count_steps) static_cast<int32_t*>(a.pl[Sys::kStepPlane])[i] = steps;
-    }
+    tile_close(sys, a, p, i, own, steps, any_reset, o);
     if (valid) {
       eval_store<1>(ev.stats, a.n, i, q, c, G, G == 0, bad);
       if constexpr (kLn) {
         float xs[KS];
-        cur_stack(st, zf, xs);
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-          if (4 * s + G < SO) p.stack_out[i * SO + 4 * s + G] = xs[s];
+        stk.cur_stack(st, zf, xs);
+        stk.store(p.stack_out, i, xs);
       }
     }
   }
@@ -3087,14 +3005,9 @@ static int launch_step_f32(const KArgs& a, const PArgs& p, const PStepArgs& st, 
 // registers) for both extractors -- the LayerNorm variant ran 4 (one per SIMD, 512
 // registers) until its frame stack was distributed over the lane groups; then 8 waves
 // measured 5.96e8 vs 4.50e8 env-steps/s at HR 32,768 x 2048 (profiles/r03/attn_f32) with
-// 20 spilled VGPRs; LZ_ATTN_F32_WAVES=4|8 forces
+// 20 spilled VGPRs
 PolShape attn_f32_policy_shape(int64_t n, int num_cus, int) {
-  static const int forced = [] {
-    const char* e = std::getenv("LZ_ATTN_F32_WAVES");
-    const int w = e ? std::atoi(e) : 0;
-    return w == 4 || w == 8 ? w : 0;
-  }();
-  PolShape s = {16, forced ? forced : 8, 0, 0};
+  PolShape s = {16, 8, 0, 0};
   const int64_t groups = ((n + 15) / 16 + s.waves - 1) / s.waves;
   s.grid = (int)(groups < num_cus ? groups : num_cus);
   return s;
@@ -3127,14 +3040,12 @@ static int launch_pol_attn_ln(int n_stack, const KArgs& a, const PArgs& p, const
 template <class Sys>
 static int launch_pol_attn_f32(int ln, int n_stack, const KArgs& a, const PArgs& p, const PolShape& sh,
                                hipStream_t s) {
-  const dim3 grid((unsigned)sh.grid), block(sh.waves * 64);
+  if (sh.waves != 8) return (int)hipErrorInvalidValue;  // attn_f32_policy_shape's
+  const dim3 grid((unsigned)sh.grid), block(8 * 64);
   const bool i8 = (p.pflags & LZ_POLICY_I8X4) != 0;
-#define LZ_ATTN_F32(LN, S_)                                                                        \
-  if (i8) {                                                                                        \
-    if (sh.waves == 8) hipLaunchKernelGGL((k_rollout_policy_attn_f32<Sys, LN, S_, 8, true>), grid, block, 0, s, a, p); \
-    else hipLaunchKernelGGL((k_rollout_policy_attn_f32<Sys, LN, S_, 4, true>), grid, block, 0, s, a, p); \
-  } else if (sh.waves == 8) hipLaunchKernelGGL((k_rollout_policy_attn_f32<Sys, LN, S_, 8>), grid, block, 0, s, a, p); \
-  else hipLaunchKernelGGL((k_rollout_policy_attn_f32<Sys, LN, S_, 4>), grid, block, 0, s, a, p);
+#define LZ_ATTN_F32(LN, S_)                                                                          \
+  if (i8) hipLaunchKernelGGL((k_rollout_policy_attn_f32<Sys, LN, S_, 8, true>), grid, block, 0, s, a, p); \
+  else hipLaunchKernelGGL((k_rollout_policy_attn_f32<Sys, LN, S_, 8>), grid, block, 0, s, a, p);
   if (!ln) { LZ_ATTN_F32(false, 1) }
   else if (n_stack == 4) { LZ_ATTN_F32(true, 4) }
   else if (n_stack == 1) { LZ_ATTN_F32(true, 1) }

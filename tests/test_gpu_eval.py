@@ -142,9 +142,11 @@ def _transitive(gl, pol, system, n, K, skip, max_episodes, sd, kw, deterministic
     ("pmsm", dict(add_noise=True, max_episode_steps=5), 4099, 12, 2, 2, True),
     ("hr", dict(add_noise=True, add_filter=True, autoreset=False), 4099, 12, 5, 0, False),
     ("lorenz4", dict(max_episode_steps=3), 70, 7, 0, 0, True),
+] + [  # 2,048 tiles = 8 per CU: the 8-wave kernel of every system, sampled actions
+    (system, dict(max_episode_steps=2), 65536, 5, 2, 0, False) for system in ("pmsm", "hr", "lorenz3", "lorenz4")
 ])
 def test_mlp_table_equals_collector(gl, pol, system, kw, n, K, skip, max_ep, det):
-    O, A = {"pmsm": (6, 2), "hr": (6, 2), "lorenz4": (8, 3)}[system]
+    O, A = {"pmsm": (6, 2), "hr": (6, 2), "lorenz3": (6, 3), "lorenz4": (8, 3)}[system]
     T = _transitive(gl, pol, system, n, K, skip, max_ep, _mlp(pol, O, A, seed=7), kw, deterministic=det)
     if kw.get("max_episode_steps"):
         assert T[er.N_EP].min() >= 1 and (T[er.N_DONE_STEPS] >= 2).all()
@@ -157,9 +159,15 @@ def test_mlp_table_equals_collector(gl, pol, system, kw, n, K, skip, max_ep, det
     ("pmsm", dict(), 777, 10, False, 1),
     ("hr", dict(), 5, 6, False, 1),                     # one partial 16-env tile
     ("hr", dict(max_episode_steps=5), 1000, 12, True, 4),   # lorenz_filter: LayerNorm + VecFrameStack(4)
+    # the other LayerNorm kernels: a full 16-env tile plus a ragged one, 2-step episodes
+    ("hr", dict(max_episode_steps=2), 17, 5, True, 1),
+    ("lorenz3", dict(max_episode_steps=2), 17, 5, True, 1),
+    ("lorenz3", dict(max_episode_steps=2), 17, 5, True, 4),
+    ("pmsm", dict(max_episode_steps=2), 17, 5, True, 1),
+    ("pmsm", dict(max_episode_steps=2), 17, 5, True, 4),
 ])
 def test_attention_table_equals_collector(gl, pol, system, kw, n, K, ln, stack):
-    sd = _attn(pol, 6 * stack, 2, seed=4, ln=ln)
+    sd = _attn(pol, 6 * stack, 3 if system == "lorenz3" else 2, seed=4, ln=ln)
     _transitive(gl, pol, system, n, K, 2, 0, sd, kw, frame_stack=stack)
 
 

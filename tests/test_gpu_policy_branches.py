@@ -25,6 +25,14 @@ Branches (MI355X: 256 CUs):
   bf16 attention  32-env waves x 4, grid-stride; LayerNorm + VecFrameStack(4 / 1)
   f32 attention   16-env waves x 8: n < 16, ragged, grid-stride; LayerNorm + stack(4)
                   grid-stride + ragged
+  i8x4            the float32 launchers' kI8 kernels (precision="i8x4"): MlpPolicy 8 waves,
+                  LayerNorm attention stack 1 / 4
+  every system    the rows after the table: each remaining (kernel, system) instantiation at
+                  its smallest size (33 / 17 envs; 129 = four split tiles plus one; 65,536 /
+                  131,072 where only the size picks the kernel), with sampled actions, the
+                  truncation bootstrap and 2-step episodes; those rows also check the
+                  log-probs and the bootstrapped rewards, and the ones above 20,000 recorded
+                  rows check the forward on 6,000 sampled rows plus the ragged tail
 """
 import numpy as np
 import pytest
@@ -36,6 +44,14 @@ pytestmark = pytest.mark.gpu
 
 F32_MLP, F32_STEP, BF16_MLP, BF16_ATTN, BF16_LN, F32_ATTN, F32_LN = (
     "f32_mlp", "f32_step", "bf16_mlp", "bf16_attn", "bf16_ln", "f32_attn", "f32_ln")
+F32_MLP_I8, F32_LN_I8 = "f32_mlp_i8", "f32_ln_i8"  # precision="i8x4": the same launchers' kI8 kernels
+# A row with a ninth field True collects with sampled actions, the truncation bootstrap and
+# 2-step episodes (K = 5: two truncations and auto-resets inside the rollout) and also checks
+# the log-probs, the noise and the bootstrapped rewards (see test_policy_branch).
+from test_gpu_policy_attn_f32 import AF_LOGSTD  # noqa: E402  (the blobs' Normal constants)
+from test_gpu_policy_f32 import F32_LOGSTD  # noqa: E402
+
+GAMMA = 0.97
 
 
 @pytest.fixture(scope="module")
@@ -120,40 +136,73 @@ CASES += [  # the LORENZ3 / PMSM arms of the kinds built for LORENZ3 / PMSM / HR
     (F32_LN, "lorenz3", 333, 4, 0, 4, "policy_attn_f32", False),
     (F32_LN, "pmsm", 333, 4, 0, 4, "policy_attn_f32", False),
 ]
-CALL = {F32_MLP: 3, F32_STEP: 4, BF16_MLP: 2, BF16_ATTN: 5, BF16_LN: 6, F32_ATTN: 7, F32_LN: 8}
+# Every remaining template instantiation of the policy kernels (one per system the kind is
+# built for), at the smallest size that reaches it: a full tile plus a ragged one where a
+# variant bit or the default picks the kernel (33 envs; 17 for the 16-env attention waves;
+# 129 = four tiles per split workgroup plus one), else the size its launcher switches at
+# (8 tiles per CU on 256 CUs = 65,536 envs; 64-env waves from 131,072).  These rows sample
+# (ninth field); the ones above 20,000 recorded rows check the forward on 6,000 sampled rows
+# and the ragged tail instead of on every row.
+_ALL = ("lorenz3", "lorenz4", "pmsm", "hr", "transient1", "transient2", "transient_pmsm", "singlecontrol")
+CASES += [(F32_MLP, "pmsm", 129, 5, 0, 1, "policy_split", False, True)]
+CASES += [(BF16_MLP, s, 33, 5, 128, 1, "policy_pair", False, True) for s in _ALL if s != "pmsm"]
+CASES += [(BF16_MLP, s, 33, 5, 32, 1, "policy", False, True) for s in _ALL if s not in ("pmsm", "lorenz3")]
+CASES += [(BF16_LN, s, 33, 5, 0, 1, "policy_attn", False, True) for s in ("lorenz3", "pmsm")]
+CASES += [(F32_MLP, s, 33, 5, 8192, 1, "policy", False, True) for s in _ALL if s not in ("pmsm", "lorenz4")]
+CASES += [(F32_STEP, "lorenz4", 33, 5, 0, 1, "policy_step", False, True)]
+CASES += [(F32_LN, s, 17, 5, 0, 1, "policy_attn_f32", False, True) for s in ("hr", "lorenz3", "pmsm")]
+CASES += [(F32_LN_I8, s, 17, 5, 0, 1, "policy_attn_f32", False, True) for s in ("hr", "lorenz3", "pmsm")]
+CASES += [(F32_LN_I8, s, 17, 5, 0, 4, "policy_attn_f32", False, True) for s in ("lorenz3", "pmsm")]
+CASES += [(BF16_MLP, s, 131072, 3, 0, 1, "policy", False, True) for s in _ALL if s != "pmsm"]
+CASES += [(F32_MLP, s, 65536, 3, 0, 1, "policy", False, True) for s in _ALL if s not in ("pmsm", "hr")]
+CASES += [(F32_MLP_I8, s, 65536, 3, 0, 1, "policy", False, True) for s in ("hr", "lorenz3", "lorenz4")]
+CASES += [(F32_STEP, s, 65536, 3, 0, 1, "policy_step", False, True) for s in _ALL if s != "lorenz4"]
+CALL = {F32_MLP: 3, F32_STEP: 4, BF16_MLP: 2, BF16_ATTN: 5, BF16_LN: 6, F32_ATTN: 7, F32_LN: 8,
+        F32_MLP_I8: 3, F32_LN_I8: 8}
 
 
-def _collector(gl, pol, kind, system, n, variant, n_stack, seed=5):
+def _collector(gl, pol, kind, system, n, variant, n_stack, seed=5, sampled=False):
     from gym_lorenz.vec_normalize import DeviceRunningMeanStd
 
-    kw = dict(max_episode_steps=3)
+    kw = dict(max_episode_steps=2 if sampled else 3)
     if system in ("pmsm", "hr"):
         kw["add_noise"] = True
     envp = gl.BatchedEnv(system, n, seed=seed, variant=variant, **kw)
     envr = gl.BatchedEnv(system, n, seed=seed, **kw)
     O, A = envp.obs_dim, envp.action_dim
+    i8 = kind in (F32_MLP_I8, F32_LN_I8)
     f32 = kind in (F32_MLP, F32_STEP, F32_ATTN, F32_LN)
-    ln = kind in (BF16_LN, F32_LN)
-    if kind in (F32_MLP, F32_STEP, BF16_MLP):
+    ln = kind in (BF16_LN, F32_LN, F32_LN_I8)
+    if kind in (F32_MLP, F32_STEP, BF16_MLP, F32_MLP_I8):
         sd = _mlp_sd(pol, O, A, seed=7, scale=0.2 if kind == BF16_MLP else 0.4)
     else:
         sd = _attn_sd(pol, n_stack * O if ln else O, A, seed=3, ln=ln)
     rms = None
     if kind == F32_STEP:  # SB3-exact VecNormalize: one launch per step
         rms = DeviceRunningMeanStd(O, envp.device)
-    col = pol.FusedRolloutCollector(envp, sd, bootstrap=False, deterministic=True, obs_rms=rms,
-                                    training=True, capture_terminal=4 * n, frame_stack=n_stack if ln else 1,
-                                    precision="fp32" if f32 else "bf16")
+    if sampled:
+        sd["log_std"] = torch.tensor([-0.5, 0.25, -0.25, 0.1][:A])
+    col = pol.FusedRolloutCollector(envp, sd, bootstrap=sampled, deterministic=not sampled, gamma=GAMMA,
+                                    obs_rms=rms, training=True, capture_terminal=4 * n, frame_stack=n_stack if ln else 1,
+                                    precision="i8x4" if i8 else "fp32" if f32 else "bf16")
     if kind == F32_STEP:
         assert col.per_step_vecnorm
     return envp, envr, col, sd, O, A
 
 
-@pytest.mark.parametrize("kind,system,n,K,variant,n_stack,kernel,stride", CASES)
-def test_policy_branch(gl, pol, orc, kind, system, n, K, variant, n_stack, kernel, stride):
+def _case_id(c):  # the ids the eight-field rows always had; "-sampled" for the others
+    return "-".join(str(v) for v in c[:8]) + ("-sampled" if len(c) > 8 and c[8] else "")
+
+
+@pytest.mark.parametrize("kind,system,n,K,variant,n_stack,kernel,stride,sampled",
+                         [tuple(c[:8]) + (len(c) > 8 and c[8],) for c in CASES],
+                         ids=[_case_id(c) for c in CASES])
+def test_policy_branch(gl, pol, orc, kind, system, n, K, variant, n_stack, kernel, stride, sampled):
     from gym_lorenz import _native as nat
 
-    envp, envr, col, sd, O, A = _collector(gl, pol, kind, system, n, variant, n_stack)
+    envp, envr, col, sd, O, A = _collector(gl, pol, kind, system, n, variant, n_stack, sampled=sampled)
+    i8 = kind in (F32_MLP_I8, F32_LN_I8)
+    exact = kind not in (BF16_MLP, BF16_ATTN, BF16_LN)
     sh = nat.launch_shape(envp._h, CALL[kind])
     assert sh["kernel"] == kernel, sh
     assert sh["grid_stride"] == stride, sh
@@ -166,7 +215,10 @@ def test_policy_branch(gl, pol, orc, kind, system, n, K, variant, n_stack, kerne
     obs_r, rew_r, done_r, (didx, tobs, nd) = envr.rollout(acts, capture_terminal=4 * n)
     # env part: bit-exact
     assert torch.equal(b.dones, done_r)
-    assert torch.equal(b.rewards, rew_r)  # no bootstrap
+    d = _np(b.dones)
+    trunc = (d & 2 != 0) & (d & 1 == 0)
+    assert np.array_equal(_np(b.rewards)[~trunc], _np(rew_r)[~trunc])  # no bootstrap there
+    assert sampled or torch.equal(b.rewards, rew_r)
     assert torch.equal(b.last_obs.view(torch.int32), obs_r[-1].view(torch.int32))
     m = int(nd.item())
     assert m > 0 and int(b.n_done.item()) == m
@@ -180,12 +232,21 @@ def test_policy_branch(gl, pol, orc, kind, system, n, K, variant, n_stack, kerne
     x = _np(b.observations).reshape(-1, I)
     act = _np(b.actions).reshape(-1, A)
     val = _np(b.values).reshape(-1)
+    logp = _np(b.log_probs).reshape(-1)
+    if sampled and x.shape[0] > 20000:  # sampled rows and the ragged tail
+        rows = np.concatenate([np.random.default_rng(0).choice(x.shape[0], 6000, replace=False),
+                               np.arange(x.shape[0] - 70, x.shape[0])])
+        x, act, val, logp = x[rows], act[rows], val[rows], logp[rows]
     if kind in (F32_MLP, F32_STEP):
         mref, vref = orc.mlp_f32(sd, x)
     elif kind in (F32_ATTN, F32_LN):
         mref, vref = orc.attn_f32(sd, x)
-    if kind in (F32_MLP, F32_STEP, F32_ATTN, F32_LN):
-        assert bits_equal(act, mref), np.nanmax(np.abs(act - mref))
+    elif kind == F32_MLP_I8:
+        mref, vref = orc.mlp_f32(sd, x, precision="i8x4")
+    elif kind == F32_LN_I8:
+        mref, vref = orc.attn_f32(sd, x, precision="i8x4")
+    if exact:
+        assert sampled or bits_equal(act, mref), np.nanmax(np.abs(act - mref))
         assert bits_equal(val, vref), np.nanmax(np.abs(val - vref))
     else:
         ref = {BF16_MLP: pol.reference_forward_bf16, BF16_ATTN: pol.reference_forward_attn_bf16,
@@ -193,11 +254,68 @@ def test_policy_branch(gl, pol, orc, kind, system, n, K, variant, n_stack, kerne
         mt, vt = ref(sd, torch.from_numpy(x))
         f = np.isfinite(x).all(1)
         tol = 2e-2 if kind == BF16_MLP else 3e-2
-        np.testing.assert_allclose(act[f], _np(mt)[f], atol=tol, rtol=tol)
+        mref = _np(mt)
+        if not sampled:
+            np.testing.assert_allclose(act[f], _np(mt)[f], atol=tol, rtol=tol)
         np.testing.assert_allclose(val[f], _np(vt)[f], atol=tol, rtol=tol)
         assert np.median(np.abs(val[f] - _np(vt)[f])) < 2e-3
+    if sampled:
+        _check_sampled(pol, orc, kind, exact, sd, col, b, x, act, mref, logp, trunc, _np(rew_r), n, O, A)
     envp.close()
     envr.close()
+
+
+def _check_sampled(pol, orc, kind, exact, sd, col, b, x, act, mref, logp, trunc, rew_r, n, O, A):
+    """The sampled rows' extra checks: the noise z = (action - mean) / scale is finite and
+    differs between rows (env, step: the Philox counter); the log-prob is the kernel's formula
+    on action - mean, bit for bit on the float32 kinds (the blob's Normal constants), within
+    tests/test_gpu_policy.py's tolerance of torch's Normal on the bf16 ones; every truncated
+    step's reward is the env's plus gamma * V(stacked terminal observation)."""
+    if exact:
+        off = AF_LOGSTD if kind in (F32_ATTN, F32_LN, F32_LN_I8) else F32_LOGSTD
+        c = np.frombuffer(_np(col.blob).tobytes(), np.float32)[off // 4: off // 4 + 16]
+        scale, var2, lscale = c[4:8], c[8:12], c[12:16]
+    else:
+        scale = np.exp(_np(sd["log_std"])).astype(np.float32)
+    f = np.isfinite(x).all(1) & np.isfinite(mref).all(1)
+    z = (act - mref)[f] / scale[:A]
+    assert np.isfinite(z).all() and len(np.unique(z[:, 0])) > 0.9 * len(z)
+    if exact:
+        dd = (act - mref).astype(np.float32)
+        lp = None
+        for j in range(A):
+            lpj = ((-(dd[:, j] * dd[:, j])) / var2[j] - lscale[j]) - np.float32(0.91893853320467274)
+            lp = lpj if lp is None else (lp + lpj).astype(np.float32)
+        assert bits_equal(logp, lp)
+    else:
+        lp = torch.distributions.Normal(torch.from_numpy(mref), torch.from_numpy(scale[:A])).log_prob(
+            torch.from_numpy(act)).sum(-1).numpy()
+        np.testing.assert_allclose(logp[f], lp[f], atol=5e-2, rtol=2e-2)
+    assert trunc.sum() > 0
+    if kind == F32_STEP:  # (its bootstrap input is normalised by the next step's statistics:
+        return            # tests/test_gpu_vecnorm_step.py restates that)
+    m = int(b.n_done.item())
+    idx = _np(b.done_idx[:m])
+    k, e = idx // n, idx % n
+    sel = trunc[k, e]
+    k, e = k[sel], e[sel]
+    if len(k) > 4000:
+        k, e, sel = k[:4000], e[:4000], np.nonzero(sel)[0][:4000]
+    # SB3's stacked terminal observation: the step's input stack rolled by one frame, the
+    # terminal frame last (one frame: the terminal observation itself)
+    st = np.concatenate([_np(b.observations)[k, e][:, O:], _np(b.terminal_obs[:m])[sel]], 1)
+    if exact:
+        fwd = orc.mlp_f32 if kind in (F32_MLP, F32_MLP_I8) else orc.attn_f32
+        _, vt = fwd(sd, st, **({"precision": "i8x4"} if kind in (F32_MLP_I8, F32_LN_I8) else {}))
+        want = (rew_r[k, e] + (np.float32(GAMMA) * vt).astype(np.float32)).astype(np.float32)
+        assert bits_equal(_np(b.rewards)[k, e], want)
+    else:
+        ref = {BF16_MLP: pol.reference_forward_bf16, BF16_ATTN: pol.reference_forward_attn_bf16,
+               BF16_LN: pol.reference_forward_attn_ln_bf16}[kind]
+        _, vt = ref(sd, torch.from_numpy(st))
+        want = np.float32(GAMMA) * _np(vt)
+        g = np.isfinite(want)
+        np.testing.assert_allclose((_np(b.rewards)[k, e] - rew_r[k, e])[g], want[g], atol=3e-2, rtol=3e-2)
 
 
 def test_bf16_mlp_shapes_bit_identical(gl, pol):

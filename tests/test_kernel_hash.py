@@ -28,6 +28,15 @@ def test_hash_found_stable_distinct():
     assert kernel_hash.kernel_code_sha256(HEAD, "/nonexistent.so") is None
 
 
+def test_all_table_matches_single_lookup():
+    """--all's table names every kernel once, with the hash the single lookup returns."""
+    table = kernel_hash.all_kernel_hashes()
+    names = [n for n, _ in table]
+    assert len(set(names)) == len(names) and names == sorted(names)
+    assert dict(table)[HEAD] == kernel_hash.kernel_code_sha256(HEAD)
+    assert dict(table)[PMSM] == kernel_hash.kernel_code_sha256(PMSM)
+
+
 def test_entry_offset_masked():
     """The masked hash ignores only the descriptor's code-entry offset: it differs from
     the whole-descriptor hash, and both are stable."""

@@ -10,6 +10,7 @@ equals the running library's (tools/pmc_summary.py and tools/pmc_sq_summary.py r
 it).  Pure Python (struct): no ROCm tools needed.
 
   python tools/kernel_hash.py <kernel mangled name> [lib.so]
+  python tools/kernel_hash.py --all [lib.so]     mangled name <tab> sha256, every kernel, sorted
 """
 import hashlib
 import os
@@ -62,13 +63,25 @@ def _symbols(elf):
             yield nm, shndx, value, size, secs
 
 
-def _sym_bytes(elf, want):
+def _sym_table(elf, only=None):
+    """name -> bytes of the defined, sized symbols of the code object (one symbol walk);
+    only: the names wanted (a single lookup copies two symbols, not every kernel)."""
+    out = {}
     for nm, shndx, value, size, secs in _symbols(elf):
-        if nm == want and 0 < shndx < len(secs) and size:
+        if only is not None and nm not in only:
+            continue
+        if nm not in out and 0 < shndx < len(secs) and size:
             sec = secs[shndx]
             start = sec["off"] + (value - sec["addr"])
-            return elf[start:start + size]
-    return None
+            out[nm] = elf[start:start + size]
+    return out
+
+
+def _kernel_sha256(syms, kernel, mask_entry=True):
+    kd = bytearray(syms.get(kernel + ".kd", b""))
+    if mask_entry and len(kd) >= 24:
+        kd[16:24] = bytes(8)  # kernel_code_entry_byte_offset: layout, not code
+    return hashlib.sha256(syms[kernel] + b"|" + bytes(kd)).hexdigest()
 
 
 def kernel_code_sha256(kernel, so_path=DEFAULT_SO, mask_entry=True):
@@ -77,18 +90,30 @@ def kernel_code_sha256(kernel, so_path=DEFAULT_SO, mask_entry=True):
     (descriptor hashed whole), for checking summaries recorded with it."""
     try:
         for elf in code_objects(so_path):
-            code = _sym_bytes(elf, kernel)
-            if code is None:
-                continue
-            kd = bytearray(_sym_bytes(elf, kernel + ".kd") or b"")
-            if mask_entry and len(kd) >= 24:
-                kd[16:24] = bytes(8)  # kernel_code_entry_byte_offset: layout, not code
-            kd = bytes(kd)
-            return hashlib.sha256(code + b"|" + kd).hexdigest()
+            syms = _sym_table(elf, (kernel, kernel + ".kd"))
+            if kernel in syms:
+                return _kernel_sha256(syms, kernel, mask_entry)
     except (OSError, struct.error, ValueError, IndexError):
         return None
     return None
 
 
+def all_kernel_hashes(so_path=DEFAULT_SO):
+    """[(mangled name, sha256)] of every kernel (every symbol with a <name>.kd descriptor)
+    in the library, sorted by name; the hashes are kernel_code_sha256's."""
+    out = []
+    for elf in code_objects(so_path):
+        syms = _sym_table(elf)
+        out += [(k, _kernel_sha256(syms, k)) for k in syms if k + ".kd" in syms]
+    return sorted(out)
+
+
 if __name__ == "__main__":
-    print(kernel_code_sha256(sys.argv[1], *(sys.argv[2:3] or [DEFAULT_SO])))
+    if len(sys.argv) < 2:
+        sys.exit(__doc__[__doc__.index("  python tools/"):])
+    so = (sys.argv[2:3] or [DEFAULT_SO])[0]
+    if sys.argv[1] == "--all":
+        for name, sha in all_kernel_hashes(so):
+            print("%s\t%s" % (name, sha))
+    else:
+        print(kernel_code_sha256(sys.argv[1], so))
