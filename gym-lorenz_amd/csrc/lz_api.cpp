@@ -1393,10 +1393,36 @@ lz_status lz_rollout_policy_attn_stack_f32(lz_handle* h, const lz_policy_rollout
 }
 
 // ---- fused policy evaluation (lorenz_env.h LZ_EVAL_*; lz_internal.h EArgs)
+// T of a trace (lorenz_env.h lz_eval_trace), or -1 for a start / every it refuses
+static int64_t trace_rows(int32_t K, int32_t start, int32_t every) {
+  if (K < 1 || every < 1 || start < 0 || start >= K) return -1;
+  return ((int64_t)K - start + every - 1) / every;
+}
+static int trace_cols(const lz::SysInfo& d, uint32_t flags) {
+  return d.obs_dim + d.action_dim + 2 + ((flags & LZ_TRACE_STATE) ? d.state_dim : 0);
+}
+
+lz_status lz_eval_trace_shape(const lz_config* cfg, int32_t K, int32_t start, int32_t every, uint32_t flags,
+                              int64_t* rows, int32_t* cols) {
+  if (!cfg || !rows || !cols) return fail(LZ_ERR_INVALID, "config/rows/cols is NULL");
+  if (cfg->system < LZ_SYS_LORENZ3 || cfg->system > LZ_SYS_SC) return fail(LZ_ERR_INVALID, "unknown system");
+  const lz::SysInfo& d = lz::sys_info(cfg->system);
+  if (!(d.policies & lz::kPolEval))
+    return fail(LZ_ERR_UNSUPPORTED, "%s", policy_row(lz::PolicyKind::EvalF32Mlp).refusal);
+  if (flags & ~LZ_TRACE_STATE) return fail(LZ_ERR_INVALID, "unknown LZ_TRACE_* flags 0x%x", flags);
+  const int64_t T = trace_rows(K, start, every);
+  if (T < 0) return fail(LZ_ERR_INVALID, "a trace needs K >= 1, every >= 1 and 0 <= start < K");
+  *rows = T;
+  *cols = trace_cols(d, flags);
+  return LZ_OK;
+}
+
+// traced: one of the *_trace entry points (tr is then required)
 static lz_status evaluate_policy(lz_handle* h, const lz_policy_eval_args* e, lz::PolicyKind kind,
                                  int n_stack = 1, const float* stack_in = nullptr,
-                                 float* stack_out = nullptr) {
-  if (!h || !e) return fail(LZ_ERR_INVALID, "handle/args is NULL");
+                                 float* stack_out = nullptr, const lz_eval_trace* tr = nullptr,
+                                 bool traced = false) {
+  if (!h || !e || (traced && !tr)) return fail(LZ_ERR_INVALID, "handle/args/trace is NULL");
   RESIDENT_QUIESCE(h);
   const PolicyRow& row = policy_row(kind);
   if (e->flags & LZ_POLICY_BOOTSTRAP)
@@ -1419,9 +1445,38 @@ static lz_status evaluate_policy(lz_handle* h, const lz_policy_eval_args* e, lz:
   if (!e->blob || !e->obs_in || !e->obs_last || !e->stats)
     return fail(LZ_ERR_INVALID, "blob / obs_in / obs_last / stats must be non-NULL");
   if (!(e->act_low <= e->act_high)) return fail(LZ_ERR_INVALID, "act_low > act_high");
+  lz::TArgs ta;
+  std::memset(&ta, 0, sizeof ta);
+  const bool trace = tr && tr->count != 0;  // count == 0: the untraced launch
+  if (tr) {
+    if (tr->count < 0) return fail(LZ_ERR_INVALID, "trace count must be >= 0");
+    if (tr->flags & ~LZ_TRACE_STATE) return fail(LZ_ERR_INVALID, "unknown LZ_TRACE_* flags 0x%x", tr->flags);
+    const int64_t T = trace_rows(e->K, tr->start, tr->every);
+    if (T < 0) return fail(LZ_ERR_INVALID, "a trace needs every >= 1 and 0 <= start < K");
+    if (trace) {
+      if (!tr->ids || !tr->slot_map || !tr->out)
+        return fail(LZ_ERR_INVALID, "trace ids / slot_map / out must be non-NULL");
+      if (tr->count > ((int64_t)1 << 31) - 1 || T * tr->count > ((int64_t)1 << 40))
+        return fail(LZ_ERR_INVALID, "trace T * count too large");
+      const int64_t need = T * tr->count * trace_cols(*h->desc, tr->flags) * (int64_t)sizeof(float);
+      if (tr->out_capacity_bytes < need)
+        return fail(LZ_ERR_INVALID, "trace out covers %lld bytes, the launch writes %lld",
+                    (long long)tr->out_capacity_bytes, (long long)need);
+      ta.slot_map = tr->slot_map;
+      ta.out = tr->out;
+      ta.m = tr->count;
+      ta.start = tr->start;
+      ta.every = tr->every;
+      ta.flags = tr->flags;
+    }
+  }
   if (!h->was_reset) return fail(LZ_ERR_STATE, "lz_evaluate_policy before the first lz_reset");
   HIP_TRY(hipSetDevice(h->cfg.device));
   const lz::PolShape sh = policy_shape_of(h, row);
+  if (trace) {
+    const int te = lz::launch_trace_slots(tr->slot_map, h->cfg.num_envs, tr->ids, tr->count, h->stream);
+    if (te != 0) return fail(LZ_ERR_HIP, "trace slot map: %s", hipGetErrorString((hipError_t)te));
+  }
   KArgs a;
   fill_common(h, a);
   a.K = e->K;
@@ -1443,7 +1498,8 @@ static lz_status evaluate_policy(lz_handle* h, const lz_policy_eval_args* e, lz:
   ev.stats = e->stats;
   ev.skip = e->skip;
   ev.max_episodes = e->max_episodes;
-  const int err = lz::launch_policy(kind, h->cfg.system, n_stack, a, p, nullptr, sh, h->stream, &ev);
+  const int err = lz::launch_policy(kind, h->cfg.system, n_stack, a, p, nullptr, sh, h->stream, &ev,
+                                    trace ? &ta : nullptr);
   if (err != 0) return fail(LZ_ERR_HIP, "policy evaluation launch: %s", hipGetErrorString((hipError_t)err));
   h->parity ^= 1;
   ++h->gen;
@@ -1461,6 +1517,21 @@ lz_status lz_evaluate_policy_attn_f32(lz_handle* h, const lz_policy_eval_args* e
 lz_status lz_evaluate_policy_attn_stack_f32(lz_handle* h, const lz_policy_eval_args* e, int32_t n_stack,
                                             const float* stack_in, float* stack_out) {
   return evaluate_policy(h, e, lz::PolicyKind::EvalF32AttnLn, n_stack, stack_in, stack_out);
+}
+
+lz_status lz_evaluate_policy_f32_trace(lz_handle* h, const lz_policy_eval_args* e, const lz_eval_trace* tr) {
+  return evaluate_policy(h, e, lz::PolicyKind::EvalF32Mlp, 1, nullptr, nullptr, tr, true);
+}
+
+lz_status lz_evaluate_policy_attn_f32_trace(lz_handle* h, const lz_policy_eval_args* e,
+                                            const lz_eval_trace* tr) {
+  return evaluate_policy(h, e, lz::PolicyKind::EvalF32Attn, 1, nullptr, nullptr, tr, true);
+}
+
+lz_status lz_evaluate_policy_attn_stack_f32_trace(lz_handle* h, const lz_policy_eval_args* e, int32_t n_stack,
+                                                  const float* stack_in, float* stack_out,
+                                                  const lz_eval_trace* tr) {
+  return evaluate_policy(h, e, lz::PolicyKind::EvalF32AttnLn, n_stack, stack_in, stack_out, tr, true);
 }
 
 lz_status lz_get_launch_shape(const lz_handle* h, int32_t call, lz_launch_shape* out) {

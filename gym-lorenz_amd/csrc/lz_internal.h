@@ -377,6 +377,18 @@ struct EArgs {
   int32_t skip;          // first in-episode step index inside the error window
   int32_t max_episodes;  // 0: every step counts
 };
+// The opt-in trace of an evaluation launch (lorenz_env.h lz_eval_trace): a kernel
+// parameter of its own, of the traced instantiations only -- EArgs and the kernels an
+// untraced launch runs stay as they are.
+struct TArgs {
+  const int32_t* slot_map;  // [N] the env's row slot, -1: not traced
+  float* out;               // [T][M][C]
+  int64_t m;                // M
+  int32_t start, every;     // step k is recorded when k >= start and (k - start) % every == 0
+  uint32_t flags;           // LZ_TRACE_*
+};
+// slot_map[0 .. n) = -1, then slot_map[ids[m]] = m for the ids inside [0, n), on stream
+int launch_trace_slots(int32_t* slot_map, int64_t n, const int64_t* ids, int64_t count, void* stream);
 
 // The integrator picks the system's instantiation: the launchers' `system` argument is
 // lz_config.system + kSysRK4 for an LZ_INT_RK4 handle of LORENZ3 / LORENZ4 (SysL3RK4 /
@@ -557,9 +569,11 @@ PolShape attn_f32_policy_shape(int64_t n, int num_cus, int variant);
 // Launch the rollout of `kind` for `system` (lz_config.system: the Euler systems);
 // hipErrorInvalidValue where the kind (or LZ_POLICY_I8X4 in F32Mlp) is not built for the
 // system (SysInfo::policies) or n_stack is not 1 or 4.  n_stack: the *AttnLn kinds';
-// st: F32MlpStep's (PStepArgs above), else nullptr; ev: the Eval* kinds' (EArgs above).
+// st: F32MlpStep's (PStepArgs above), else nullptr; ev: the Eval* kinds' (EArgs above);
+// tr: an Eval* launch's trace (TArgs above: the traced instantiation of the same shape).
 int launch_policy(PolicyKind kind, int system, int n_stack, const KArgs& a, const PArgs& p,
-                  const PStepArgs* st, const PolShape& sh, void* stream, const EArgs* ev = nullptr);
+                  const PStepArgs* st, const PolShape& sh, void* stream, const EArgs* ev = nullptr,
+                  const TArgs* tr = nullptr);
 // the evaluation launches' shapes: f32_policy_shape's wave count with pair = 0 (one wave
 // per 32-env tile: there is no critic to split off) / 16-env waves, 8 per workgroup
 PolShape eval_f32_policy_shape(int64_t n, int num_cus, int variant);

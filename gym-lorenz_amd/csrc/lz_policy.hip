@@ -2610,191 +2610,67 @@ __device__ __forceinline__ void eval_store(double* stats, int64_t n, int64_t i, 
 }
 static_assert(LZ_EVAL_SQ_SUM0 == 4 && LZ_EVAL_MAX_ABS0 == 8 && LZ_EVAL_COLS == 24, "table columns");
 
-// The float32 MlpPolicy (kF32* blob): one wave per 32-env tile as k_rollout_policy's
-// kMlpF32 path, the pi net, the Normal constants and the tanh table alone in LDS (75 KB
-// of the blob's 148).
-template <class Sys, int W>
-__global__ __launch_bounds__(W * 64) void k_evaluate_policy_f32(KArgs a, PArgs p, EArgs ev) {
-  constexpr int E = 32;
-  constexpr int O = Sys::O, A = Sys::A, ED = O / 2;
-  constexpr int kCst = 64 + kTanhSegs * 32;
-  static_assert(O <= kPolMaxObs && A <= kPolMaxAct && ED <= 4, "policy tile shape");
-  static_assert(kF32Net % 16 == 0 && kF32LogStd % 16 == 0 && kCst % 16 == 0 && kF32Tag + 16 <= kF32Net,
-                "16-B pieces");
-  __shared__ __attribute__((aligned(64))) uint8_t s_net[kF32Net];
-  __shared__ __attribute__((aligned(16))) uint8_t s_cst[kCst];
-  __shared__ double s_norm[2 * kPolMaxObs];
-  const int tid = (int)threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6, h = lane >> 5;
-  const int slot = lane & 31;
-  const bool owner = h == 0;
-  const bool bad = !blob_is(p.blob, kF32Tag, LZ_BLOB_MLP_F32);
-  blob_to_lds(reinterpret_cast<f4v*>(s_net), reinterpret_cast<const f4v*>(p.blob), kF32Net / 16, tid,
-              W * 64, bad);
-  blob_to_lds(reinterpret_cast<f4v*>(s_cst), reinterpret_cast<const f4v*>(p.blob + kF32LogStd), kCst / 16,
-              tid, W * 64, bad);
-  const uint64_t tick = pol_prologue<O>(a, p, s_norm, tid);
-  __syncthreads();
-  const float* g_scale = reinterpret_cast<const float*>(s_cst) + 4;
-  const float* ttab = reinterpret_cast<const float*>(s_cst + 64);
-  const bool norm = p.norm != nullptr;
-  const double* mu = s_norm;
-  const double* sd = s_norm + kPolMaxObs;
-  const bool det = (p.pflags & LZ_POLICY_DETERMINISTIC) != 0;
-  const bool autoreset = (a.flags & LZ_FLAG_AUTORESET) != 0;
-  Sys sys;
-  sys.setup(a);
-  const int64_t ntiles = (a.n + E - 1) / E;
-  for (int64_t tile = (int64_t)blockIdx.x * W + wave; tile < ntiles; tile += (int64_t)gridDim.x * W) {
-    const int64_t i = tile * E + slot;
-    const bool live = owner && i < a.n;
-    int32_t steps;
-    bool any_reset = false;
-    double q[4][4];  // this tile's accumulators: zeroed per grid-stride tile
-    EvalCount c;
-    eval_zero<4>(q, c);
-    float o[O];
-    tile_open(sys, a, p, i, live, steps, o);
-    for (int k = 0; k < a.K; ++k) {
-      float x[O];
-      normalize<O>(o, x, norm, mu, sd, p.clip);
-      float mean[A];
-      float xs[(O + 1) / 2];
-      f32_inputs<O, (O + 1) / 2>(x, lane, xs);
-      mlp_f32<(O + 1) / 2, A>(s_net, xs, lane, mean, ttab);
-      float act_c[A];
-      if (live) {
-        float act[A];
-        policy_sample<A, false>(a, p, i, tick + (uint64_t)k, det, mean, g_scale, act, act_c);
-      }
-      float on[O], ot[O];
-      float rew = 0.0f;
-      bool did_reset;
-      const uint8_t df = step_body<Sys, float, true, true>(sys, steps, a, i, live, act_c,
-                                                           tick + (uint64_t)k, k, on, rew, did_reset, ot);
-      any_reset = any_reset || did_reset;
-      if (live) eval_step<4, ED>(q, c, 0, ot, rew, df, k, autoreset, ev.skip, ev.max_episodes);
+// The opt-in trace (lorenz_env.h lz_eval_trace; TArgs): the lane that owns a traced env
+// stores one row per recorded step: row t of slot `slot` (TraceCursor below keeps both).
+// bad: the blob's format tag did not match -- the row is NaN like the table.
+template <class Sys>
+__device__ __forceinline__ void trace_row(const TArgs& tr, const Sys& sys, int32_t slot, int t, const float* o,
+                                          const float* act_c, float r, uint8_t d, bool bad) {
+  constexpr int O = Sys::O, A = Sys::A, SD = Sys::state_dim;
+  const bool with_state = (tr.flags & LZ_TRACE_STATE) != 0;
+  const int C = O + A + 2 + (with_state ? SD : 0);
+  float* row = tr.out + ((int64_t)t * tr.m + slot) * C;
+  const float qn = __builtin_nanf("");
 #pragma unroll
-      for (int j = 0; j < O; ++j) o[j] = on[j];
-    }
-    tile_close(sys, a, p, i, live, steps, any_reset, o);
-    if (live) eval_store<4>(ev.stats, a.n, i, q, c, 0, true, bad);
+  for (int j = 0; j < O; ++j) row[j] = bad ? qn : o[j];
+#pragma unroll
+  for (int j = 0; j < A; ++j) row[O + j] = bad ? qn : act_c[j];
+  row[O + A] = bad ? qn : r;
+  row[O + A + 1] = bad ? qn : (float)d;
+  if (with_state) {
+    float sv[SD];
+    sys.trace_state(sv);
+#pragma unroll
+    for (int j = 0; j < SD; ++j) row[O + A + 2 + j] = bad ? qn : sv[j];
   }
 }
 
-// The float32 attention actor-critics (kAF* blob; kLn: the residual + LayerNorm extractor
-// on an S-frame VecFrameStack): 16-env waves as k_rollout_policy_attn_f32.  There is one
-// net to run, so the pi net is DMA'd into the slot once per launch and stays: the step
-// loop has no barrier and no slot swap.  The stack lives distributed over the lane groups
-// and follows the rollout's order exactly (the zeroing of a done env's older frames is
-// applied when the next input is formed).
-template <class Sys, bool kLn, int S, int W>
-__global__ __launch_bounds__(W * 64) void k_evaluate_policy_attn_f32(KArgs a, PArgs p, EArgs ev) {
-  constexpr int E = 16;
-  constexpr int O = Sys::O, A = Sys::A, ED = O / 2;
-  using Stack = AttnStack<O, S>;
-  constexpr int SO = Stack::SO, KS = Stack::KS;
-  static_assert(kLn || S == 1, "frame stacking is the LayerNorm variant's");
-  static_assert(SO <= kAFMaxIn && O <= kPolMaxObs && A <= kPolMaxAct && ED <= 4, "policy tile shape");
-  __shared__ __attribute__((aligned(16))) uint8_t s_lds[kAFLdsBytes];
-  __shared__ double s_norm[2 * kPolMaxObs];
-  const int tid = (int)threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6, G = lane >> 4, col = lane & 15;
-  const bool bad = !blob_is(p.blob, kAFTag, kLn ? LZ_BLOB_ATTN_LN_F32 : LZ_BLOB_ATTN_F32);
-  blob_to_lds(reinterpret_cast<f4v*>(s_lds), reinterpret_cast<const f4v*>(p.blob), kAFExt / 16, tid, W * 64,
-              bad);
-  blob_to_lds(reinterpret_cast<f4v*>(s_lds + kAFExt), reinterpret_cast<const f4v*>(p.blob + kAFLogStd),
-              kAFConst / 16, tid, W * 64, bad);
-  const uint64_t tick = pol_prologue<O>(a, p, s_norm, tid);
-  const uint8_t* s_ext = s_lds;
-  const float* cst = reinterpret_cast<const float*>(s_lds + kAFExt);
-  const float* g_scale = cst + 4;
-  const float* ttab = cst + 16;
-  const uint8_t* s_net = s_lds + kAFExt + kAFConst;
-  net_dma<W>(p.blob + kAFPi, s_net, wave, lane);  // the pi net into the slot, once
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // this wave's DMA pieces have landed
-  __syncthreads();
-  const bool norm = p.norm != nullptr;
-  const double* mu = s_norm;
-  const double* sd = s_norm + kPolMaxObs;
-  const bool det = (p.pflags & LZ_POLICY_DETERMINISTIC) != 0;
-  const bool autoreset = (a.flags & LZ_FLAG_AUTORESET) != 0;
-  Sys sys;
-  sys.setup(a);
-  const int64_t ntiles = (a.n + E - 1) / E;
-  const Stack stk = {G, col};
-  for (int64_t tile = (int64_t)blockIdx.x * W + wave; tile < ntiles; tile += (int64_t)gridDim.x * W) {
-    const int64_t i = tile * E + col;
-    const bool valid = i < a.n;        // all four lanes of the env compute it
-    const bool own = valid && G == 0;  // ... lane group 0 stores it
-    int32_t steps;
-    bool any_reset = false;
-    double q[1][4];  // lane group G's part of this tile's accumulators, zeroed per tile
-    EvalCount c;
-    eval_zero<1>(q, c);
-    float o[O], st[kLn ? KS : 1];
-    bool zf = false;
-    // tile_open written out: called, the HR instance of this kernel measured 0.27 % slower
-    // (five alternating rounds against the previous code, its spread 0.22 %); with this
-    // block in place and every other shared step called, -0.02 %
-    steps = 0;
-#pragma unroll
-    for (int j = 0; j < O; ++j) o[j] = 0.0f;
-    if (valid) {
-      sys.load(a, i);
-      if (a.count_steps) steps = static_cast<const int32_t*>(a.pl[Sys::kStepPlane])[i];
-#pragma unroll
-      for (int j = 0; j < O; ++j) o[j] = p.obs_in[i * O + j];
-    }
-    if constexpr (kLn) stk.load(p.stack_in, i, valid, st);
-    for (int k = 0; k < a.K; ++k) {
-      f32x4 F[4];
-      float xs[KS];
-      if constexpr (kLn) {
-        stk.cur_stack(st, zf, xs);
-      } else {
-        float x[O];
-        normalize<O>(o, x, norm, mu, sd, p.clip);
-        stk.inputs(x, xs);
-      }
-      attn16_extract<KS, kLn>(s_ext, xs, lane, F);
-      float mean[A];
-      attn16_net<A>(s_net, F, lane, mean, ttab);
-      float act_c[A];
-#pragma unroll
-      for (int j = 0; j < A; ++j) act_c[j] = 0.0f;
-      if (valid) {  // every lane of the env: the same Philox draw
-        float act[A];
-        policy_sample<A, false>(a, p, i, tick + (uint64_t)k, det, mean, g_scale, act, act_c);
-      }
-      // the deferred zeroing of a done env's older frames
-      if constexpr (kLn) stk.cur_stack(st, zf, st);
-      float on[O], ot[O];
-      float rew = 0.0f;
-      bool did_reset;
-      const uint8_t df = step_body<Sys, float, true, true>(sys, steps, a, i, valid, act_c,
-                                                           tick + (uint64_t)k, k, on, rew, did_reset, ot,
-                                                           G == 0);
-      any_reset = any_reset || did_reset;
-      if (valid) eval_step<1, ED>(q, c, G, ot, rew, df, k, autoreset, ev.skip, ev.max_episodes);
-      if constexpr (kLn) {
-        stk.roll_stack(st, on);
-        zf = df != 0;
-      }
-#pragma unroll
-      for (int j = 0; j < O; ++j) o[j] = on[j];
-    }
-    tile_close(sys, a, p, i, own, steps, any_reset, o);
-    if (valid) {
-      eval_store<1>(ev.stats, a.n, i, q, c, G, G == 0, bad);
-      if constexpr (kLn) {
-        float xs[KS];
-        stk.cur_stack(st, zf, xs);
-        stk.store(p.stack_out, i, xs);
-      }
-    }
+// A lane's place in the trace: its env's slot and the next recorded step / row (the
+// same in every lane: the test k == next is wave-uniform).
+struct TraceCursor {
+  int32_t slot;
+  int next, row;
+  // own: this lane stores its env's rows
+  __device__ __forceinline__ void open(const TArgs& tr, int64_t i, bool own) {
+    slot = own ? tr.slot_map[i] : -1;
+    next = tr.start;
+    row = 0;
   }
+  template <class Sys>
+  __device__ __forceinline__ void step(const TArgs& tr, const Sys& sys, int k, const float* o, const float* act_c,
+                                       float r, uint8_t d, bool bad) {
+    if (k != next) return;
+    if (slot >= 0) trace_row(tr, sys, slot, row, o, act_c, r, d, bad);
+    next += tr.every;
+    row += 1;
+  }
+};
+
+__global__ __launch_bounds__(256) void k_trace_slots(int32_t* slot_map, int64_t n, const int64_t* ids,
+                                                     int64_t count) {
+  const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (m >= count) return;
+  const int64_t id = ids[m];
+  if (id >= 0 && id < n) slot_map[id] = (int32_t)m;
 }
+
+// k_evaluate_policy_f32 / k_evaluate_policy_attn_f32 and their traced forms
+#define LZ_EVAL_TRACE 0
+#include "lz_eval_kernels.inc"
+#undef LZ_EVAL_TRACE
+#define LZ_EVAL_TRACE 1
+#include "lz_eval_kernels.inc"
+#undef LZ_EVAL_TRACE
 
 // obs moments: out = (count, column sums, column sums of squares) from the per-wave
 // partials, summed in a fixed order.  One workgroup per column (the column loop ran in
@@ -3072,8 +2948,16 @@ PolShape eval_attn_f32_policy_shape(int64_t n, int num_cus, int) {
 }
 
 template <class Sys>
-static int launch_eval_f32(const KArgs& a, const PArgs& p, const EArgs& ev, const PolShape& sh,
+static int launch_eval_f32(const KArgs& a, const PArgs& p, const EArgs& ev, const TArgs* tr, const PolShape& sh,
                            hipStream_t s) {
+  const dim3 grid((unsigned)sh.grid);
+  if (tr) {  // the traced instantiation of the same shape
+    if (sh.waves == 4)
+      hipLaunchKernelGGL((k_evaluate_policy_f32_trace<Sys, 4>), grid, dim3(4 * 64), 0, s, a, p, ev, *tr);
+    else
+      hipLaunchKernelGGL((k_evaluate_policy_f32_trace<Sys, 8>), grid, dim3(8 * 64), 0, s, a, p, ev, *tr);
+    return (int)hipGetLastError();
+  }
   if (sh.waves == 4)
     hipLaunchKernelGGL((k_evaluate_policy_f32<Sys, 4>), dim3((unsigned)sh.grid), dim3(4 * 64), 0, s, a, p, ev);
   else
@@ -3083,11 +2967,14 @@ static int launch_eval_f32(const KArgs& a, const PArgs& p, const EArgs& ev, cons
 
 template <class Sys>
 static int launch_eval_attn_f32(int ln, int n_stack, const KArgs& a, const PArgs& p, const EArgs& ev,
-                                const PolShape& sh, hipStream_t s) {
+                                const TArgs* tr, const PolShape& sh, hipStream_t s) {
   if (sh.waves != 8) return (int)hipErrorInvalidValue;  // eval_attn_f32_policy_shape's
   const dim3 grid((unsigned)sh.grid), block(8 * 64);
-#define LZ_EVAL_ATTN(LN, S_) \
-  hipLaunchKernelGGL((k_evaluate_policy_attn_f32<Sys, LN, S_, 8>), grid, block, 0, s, a, p, ev);
+#define LZ_EVAL_ATTN(LN, S_)                                                                              \
+  if (tr)                                                                                                 \
+    hipLaunchKernelGGL((k_evaluate_policy_attn_f32_trace<Sys, LN, S_, 8>), grid, block, 0, s, a, p, ev, *tr); \
+  else                                                                                                    \
+    hipLaunchKernelGGL((k_evaluate_policy_attn_f32<Sys, LN, S_, 8>), grid, block, 0, s, a, p, ev);
   if (!ln) { LZ_EVAL_ATTN(false, 1) }
   else if (n_stack == 4) { LZ_EVAL_ATTN(true, 4) }
   else if (n_stack == 1) { LZ_EVAL_ATTN(true, 1) }
@@ -3100,7 +2987,7 @@ static int launch_eval_attn_f32(int ln, int n_stack, const KArgs& a, const PArgs
 // launcher; a kind the system list (lz_dispatch.h) does not name for the system is not
 // instantiated for it and refused here (lz_api.cpp refuses it first, with a message).
 int launch_policy(PolicyKind kind, int system, int n_stack, const KArgs& a, const PArgs& p,
-                  const PStepArgs* st, const PolShape& sh, void* stream, const EArgs* ev) {
+                  const PStepArgs* st, const PolShape& sh, void* stream, const EArgs* ev, const TArgs* tr) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   return for_system(system, false, [&](auto tag) -> int {
     using Tag = decltype(tag);
@@ -3132,22 +3019,31 @@ int launch_policy(PolicyKind kind, int system, int n_stack, const KArgs& a, cons
         break;
       case PolicyKind::EvalF32Mlp:
         if constexpr (Tag::runs(PolicyKind::EvalF32Mlp)) {
-          if (ev) return launch_eval_f32<Sys>(a, p, *ev, sh, s);
+          if (ev) return launch_eval_f32<Sys>(a, p, *ev, tr, sh, s);
         }
         break;
       case PolicyKind::EvalF32Attn:
         if constexpr (Tag::runs(PolicyKind::EvalF32Attn)) {
-          if (ev) return launch_eval_attn_f32<Sys>(0, n_stack, a, p, *ev, sh, s);
+          if (ev) return launch_eval_attn_f32<Sys>(0, n_stack, a, p, *ev, tr, sh, s);
         }
         break;
       case PolicyKind::EvalF32AttnLn:
         if constexpr (Tag::runs(PolicyKind::EvalF32AttnLn)) {
-          if (ev) return launch_eval_attn_f32<Sys>(1, n_stack, a, p, *ev, sh, s);
+          if (ev) return launch_eval_attn_f32<Sys>(1, n_stack, a, p, *ev, tr, sh, s);
         }
         break;
     }
     return (int)hipErrorInvalidValue;
   });
+}
+
+int launch_trace_slots(int32_t* slot_map, int64_t n, const int64_t* ids, int64_t count, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const hipError_t e = hipMemsetAsync(slot_map, 0xFF, (size_t)n * sizeof(int32_t), s);  // -1 everywhere
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(k_trace_slots, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, slot_map, n, ids,
+                     count);
+  return (int)hipGetLastError();
 }
 
 int launch_policy_moments_final(const double* partials, int nparts, int width, double count,

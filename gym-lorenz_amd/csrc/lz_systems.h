@@ -122,6 +122,8 @@ struct SysL3 {
   __device__ void store(const KArgs& a, int64_t i) const {
     st<T>(a.pl[0], i, x); st<T>(a.pl[1], i, y); st<T>(a.pl[2], i, z);
   }
+  // the state_dim leading planes' values as held now (the evaluation trace, LZ_TRACE_STATE)
+  __device__ void trace_state(float* v) const { v[0] = (float)x; v[1] = (float)y; v[2] = (float)z; }
   __device__ void store_reset(const KArgs& a, int64_t i) const { store(a, i); }
   __device__ void store_autoreset_extra(const KArgs&, int64_t) const {}
   // dynamic.py:39-41 (reset) / :70-72 / :77-79 (step)
@@ -183,6 +185,10 @@ struct SysL4 {
   __device__ void store(const KArgs& a, int64_t i) const {
 #pragma unroll
     for (int j = 0; j < 4; ++j) { st<T>(a.pl[j], i, m[j]); st<T>(a.pl[4 + j], i, s[j]); }
+  }
+  __device__ void trace_state(float* v) const {  // master x1..x4, slave x1..x4
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { v[j] = (float)m[j]; v[4 + j] = (float)s[j]; }
   }
   __device__ void store_reset(const KArgs& a, int64_t i) const { store(a, i); }
   __device__ void store_autoreset_extra(const KArgs&, int64_t) const {}
@@ -348,6 +354,10 @@ struct SysPMSM {
     for (int j = 0; j < 3; ++j) { st<float>(a.pl[j], i, s1[j]); st<float>(a.pl[3 + j], i, s2[j]); }
     st<float>(a.pl[6], i, lam); st<float>(a.pl[7], i, mt); st<float>(a.pl[8], i, vt);
     st<int32_t>(a.pl[9], i, adam);
+  }
+  __device__ void trace_state(float* v) const {  // state1, state2
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { v[j] = s1[j]; v[3 + j] = s2[j]; }
   }
   // reset(): Adam m/v/step and lambda are NOT reset (:59-75)
   __device__ void store_reset(const KArgs& a, int64_t i) const {
@@ -656,6 +666,10 @@ struct SysHR {
 #pragma unroll
     for (int j = 0; j < 3; ++j) { st<T>(a.pl[j], i, m[j]); st<T>(a.pl[3 + j], i, s[j]); }
     if (a.flags & LZ_FLAG_ADD_FILTER) { st<float>(a.pl[7], i, fa0); st<float>(a.pl[8], i, fa1); }
+  }
+  __device__ void trace_state(float* v) const {  // master, slave
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { v[j] = (float)m[j]; v[3 + j] = (float)s[j]; }
   }
   __device__ void store_reset(const KArgs& a, int64_t i) const {  // :55-69
 #pragma unroll

@@ -157,6 +157,22 @@ class LzPolicyEvalArgs(ctypes.Structure):
     ]
 
 
+class LzEvalTrace(ctypes.Structure):
+    """lz_eval_trace (lz_evaluate_policy_*_f32_trace)."""
+    _fields_ = [
+        ("ids", ctypes.c_void_p),
+        ("count", ctypes.c_int64),
+        ("slot_map", ctypes.c_void_p),
+        ("start", ctypes.c_int32),
+        ("every", ctypes.c_int32),
+        ("flags", ctypes.c_uint32),
+        ("out", ctypes.c_void_p),
+        ("out_capacity_bytes", ctypes.c_int64),
+    ]
+
+
+TRACE_STATE = 1  # LZ_TRACE_STATE
+
 # columns of the evaluation table (lorenz_env.h LZ_EVAL_*): float64 [EVAL_COLS, N]
 (EVAL_ABS_SUM0, EVAL_SQ_SUM0, EVAL_MAX_ABS0) = 0, 4, 8
 (EVAL_N_WIN, EVAL_RET_SUM, EVAL_N_STEPS, EVAL_N_EP, EVAL_EP_RET_SUM, EVAL_EP_RET_SQ,
@@ -275,6 +291,16 @@ _SIGS = {
     "lz_evaluate_policy_attn_f32": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyEvalArgs)]),
     "lz_evaluate_policy_attn_stack_f32": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyEvalArgs),
                                                          ctypes.c_int32, VP, VP]),
+    "lz_eval_trace_shape": (ctypes.c_int, [ctypes.POINTER(LzConfig), ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64),
+                                           ctypes.POINTER(ctypes.c_int32)]),
+    "lz_evaluate_policy_f32_trace": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyEvalArgs),
+                                                    ctypes.POINTER(LzEvalTrace)]),
+    "lz_evaluate_policy_attn_f32_trace": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyEvalArgs),
+                                                         ctypes.POINTER(LzEvalTrace)]),
+    "lz_evaluate_policy_attn_stack_f32_trace": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyEvalArgs),
+                                                               ctypes.c_int32, VP, VP,
+                                                               ctypes.POINTER(LzEvalTrace)]),
     "lz_gae": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, VP, VP, VP, VP, ctypes.c_double,
                               ctypes.c_double, VP, VP, ctypes.c_int32, VP]),
     "lz_episode_starts": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, VP, VP, VP, VP,

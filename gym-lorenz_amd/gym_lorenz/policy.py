@@ -29,7 +29,9 @@ time-major device tensors in SB3's RolloutBuffer layout ([K, N, ...]).
 afterwards (its ``test_evaluate.py`` scripts, SB3 ``evaluate_policy``): the same closed
 loop without the value net, the bootstrap and the [K, N, *] buffers, the MAE / RMSE /
 episode-return statistics kept as per-env float64 running sums on the device
-(``lz_evaluate_policy_f32`` / ``_attn_f32`` / ``_attn_stack_f32``).
+(``lz_evaluate_policy_f32`` / ``_attn_f32`` / ``_attn_stack_f32``).  With ``trace=ids`` the
+same launch also records those envs' per-step trajectories (``EvalTrace``: the scripts'
+error / control curves and state records).
 
 ``ActorCriticMlp`` is a plain-torch restatement of SB3's ActorCriticPolicy for this
 net_arch (same state_dict keys, same orthogonal init) -- the weight source when SB3 is
@@ -46,6 +48,7 @@ import torch.distributed as dist
 from torch import nn
 
 from . import _native as nat
+from .core import check_buffer
 from .registry import LEGACY_SPECS, SPECS
 
 HIDDEN = nat.POLICY_HIDDEN
@@ -810,6 +813,102 @@ class FusedRolloutCollector:
 # it back; the other systems' observations carry the error itself.
 ERR_SCALE = {"lorenz3": 1.0, "lorenz4": 1.0, "pmsm": 1.0, "hr": 50.0}
 ERR_DIMS = {"lorenz3": 3, "lorenz4": 4, "pmsm": 3, "hr": 3}
+# ... and the factor they multiply the action by before they plot it as the control signal
+# (code/test_evaluate.py:127-128 action * 100 for HR; the other systems' scripts keep the action)
+CTRL_SCALE = {"lorenz3": 1.0, "lorenz4": 1.0, "pmsm": 1.0, "hr": 100.0}
+# the leading state planes LZ_TRACE_STATE appends to a trace row (lorenz_env.h)
+STATE_DIMS = {"lorenz3": 3, "lorenz4": 8, "pmsm": 6, "hr": 6}
+
+
+def trace_shape(K, start=0, every=1):
+    """T, the rows of a trace of K steps: step k is recorded when k >= start and
+    (k - start) % every == 0.  Refuses what lz_eval_trace_shape refuses."""
+    K, start, every = int(K), int(start), int(every)
+    if K < 1 or every < 1 or start < 0 or start >= K:
+        raise ValueError("a trace needs K >= 1, trace_every >= 1 and 0 <= trace_start < K "
+                         "(K=%d, trace_start=%d, trace_every=%d)" % (K, start, every))
+    return -(-(K - start) // every)
+
+
+def validate_trace_ids(ids, num_envs):
+    """The env ids of a trace as a list of ints: at least one, each in [0, num_envs), no
+    repeats (at the C level a repeated id leaves it open which of its rows is written)."""
+    if isinstance(ids, torch.Tensor):
+        if ids.is_floating_point() or ids.dtype == torch.bool:
+            raise ValueError("trace ids must be integers, got %s" % ids.dtype)
+        ids = ids.detach().cpu().reshape(-1).tolist()
+    else:
+        ids = [i for i in np.asarray(ids).reshape(-1).tolist()]
+        if any(not isinstance(i, int) or isinstance(i, bool) for i in ids):
+            raise ValueError("trace ids must be integers")
+    if not ids:
+        raise ValueError("trace needs at least one env id (trace=None evaluates without a trace)")
+    bad = [i for i in ids if not 0 <= i < num_envs]
+    if bad:
+        raise ValueError("trace ids outside [0, %d): %s" % (num_envs, bad[:8]))
+    if len(set(ids)) != len(ids):
+        seen, dup = set(), []
+        for i in ids:
+            if i in seen:
+                dup.append(i)
+            seen.add(i)
+        raise ValueError("trace ids repeat: %s" % sorted(set(dup))[:8])
+    return ids
+
+
+class EvalTrace:
+    """The per-step record of the traced envs of one ``FusedEvaluator.evaluate(...,
+    trace=ids)`` launch: views into ``data``, the float32 [T, M, C] buffer the launch wrote
+    (lorenz_env.h lz_eval_trace), row t = step ``steps[t]``, slot m = env ``env_ids[m]``.
+
+    obs [T, M, O]      the observation each step emitted before any auto-reset
+    actions [T, M, A]  the clipped action the env was stepped with (model.predict's)
+    rewards [T, M]     the env reward
+    dones [T, M]       uint8 LZ_DONE_* bits
+    state [T, M, S]    with trace_state: the leading state planes after the step, else None
+    steps [T]          int64, the step index k of each row
+    env_ids [M]        int64
+    """
+
+    def __init__(self, data, system_name, obs_dim, action_dim, with_state, start, every, env_ids):
+        O, A = int(obs_dim), int(action_dim)
+        S = STATE_DIMS[system_name] if with_state else 0
+        if data.dim() != 3 or data.shape[2] != O + A + 2 + S:
+            raise ValueError("trace data must be [T, M, %d], got %s" % (O + A + 2 + S, tuple(data.shape)))
+        self.data = data
+        self.system_name = system_name
+        self.obs = data[..., :O]
+        self.actions = data[..., O:O + A]
+        self.rewards = data[..., O + A]
+        self.dones = data[..., O + A + 1].to(torch.uint8)
+        self.state = data[..., O + A + 2:] if with_state else None
+        self.start, self.every = int(start), int(every)
+        self.steps = self.start + self.every * torch.arange(data.shape[0], dtype=torch.int64,
+                                                            device=data.device)
+        self.env_ids = torch.as_tensor(env_ids, dtype=torch.int64).to(data.device)
+
+    def errors(self):
+        """[T, M, ED] the synchronisation error as the reference records it (err_x / err_y /
+        err_z = obs[:3] * 50 for HR; the other systems' observations carry it unscaled)."""
+        return self.obs[..., :ERR_DIMS[self.system_name]] * ERR_SCALE[self.system_name]
+
+    def controls(self):
+        """[T, M, A] the control signal as the reference plots it (ctrl_x / ctrl_y =
+        action * 100 for HR, the action itself elsewhere)."""
+        return self.actions * CTRL_SCALE[self.system_name]
+
+    def time(self, dt):
+        """[T] float64: the reference's time axis, step * dt."""
+        return self.steps.to(torch.float64) * float(dt)
+
+    def numpy(self):
+        """Everything on the host, one dict of NumPy arrays (errors / controls included)."""
+        out = {k: getattr(self, k).cpu().numpy() for k in ("obs", "actions", "rewards", "dones", "steps",
+                                                           "env_ids")}
+        out["state"] = None if self.state is None else self.state.cpu().numpy()
+        out["errors"] = self.errors().cpu().numpy()
+        out["controls"] = self.controls().cpu().numpy()
+        return out
 
 
 class EvalResult:
@@ -821,10 +920,12 @@ class EvalResult:
     ``pooled_sums`` is the float64 device tensor [EVAL_COLS] of column sums over this
     handle's envs; a multi-rank caller all-reduces it (SUM) and passes it back through
     ``EvalResult.pool``.  The max / first-done / done-bit columns do not pool by a sum:
-    ``max_abs`` is taken over the table itself."""
+    ``max_abs`` is taken over the table itself.  ``trace``: the EvalTrace of a traced
+    launch, else None."""
 
-    def __init__(self, stats, system_name):
+    def __init__(self, stats, system_name, trace=None):
         self.stats = stats
+        self.trace = trace
         self.system_name = system_name
         self.err_dims = ERR_DIMS[system_name]
         self.err_scale = ERR_SCALE[system_name]
@@ -963,13 +1064,41 @@ class FusedEvaluator:
         self.last_stack[:, -self.O:] = obs
         return self.last_obs
 
-    def evaluate(self, K, skip=0, max_episodes=0):
+    def evaluate(self, K, skip=0, max_episodes=0, trace=None, trace_every=1, trace_start=0,
+                 trace_state=False, trace_out=None, trace_slot_map=None):
         """K closed-loop steps in one launch -> EvalResult.  skip: in-episode step index
         from which the error window opens (the reference's ``step >= 1000``);
-        max_episodes: episodes counted per env (0: every step counts)."""
+        max_episodes: episodes counted per env (0: every step counts).
+
+        trace: env ids (a sequence or tensor, no repeats) whose trajectories the launch
+        records besides the table -> ``EvalResult.trace`` (EvalTrace): steps trace_start,
+        trace_start + trace_every, ... whatever skip and max_episodes say; trace_state adds
+        the state planes (the master and slave states).  trace_out / trace_slot_map:
+        caller-owned buffers for the rows (float32, >= T * M * C elements) and the launch's
+        slot map (int32 [N]); allocated here when None."""
         if self.last_obs is None:
             self.reset()
         n, O, dev = self.n, self.O, self.device
+        tr = None
+        if trace is not None:
+            T = trace_shape(K, trace_start, trace_every)
+            ids = validate_trace_ids(trace, n)
+            M = len(ids)
+            C = O + self.A + 2 + (STATE_DIMS[self.env.system_name] if trace_state else 0)
+            if trace_out is None:
+                trace_out = torch.empty((T * M * C,), dtype=torch.float32, device=dev)
+            if trace_slot_map is None:
+                trace_slot_map = torch.empty((n,), dtype=torch.int32, device=dev)
+            ids_dev = torch.tensor(ids, dtype=torch.int64, device=dev)
+            tr = nat.LzEvalTrace()
+            tr.ids, tr.count = _p(ids_dev), M
+            tr.slot_map = check_buffer(trace_slot_map, "trace_slot_map", torch.int32, n, dev)
+            tr.start, tr.every = int(trace_start), int(trace_every)
+            tr.flags = nat.TRACE_STATE if trace_state else 0
+            tr.out = check_buffer(trace_out, "trace_out", torch.float32, T * M * C, dev, at_least=True)
+            tr.out_capacity_bytes = trace_out.numel() * 4
+        elif trace_every != 1 or trace_start != 0 or trace_state or trace_out is not None:
+            raise ValueError("trace_every / trace_start / trace_state / trace_out need trace=ids")
         stats = torch.empty((nat.EVAL_COLS, n), dtype=torch.float64, device=dev)
         obs_last = torch.empty((n, O), dtype=torch.float32, device=dev)
         e = nat.LzPolicyEvalArgs()
@@ -990,19 +1119,31 @@ class FusedEvaluator:
         stack_out = None
         if self.attention_ln:
             stack_out = torch.empty((n, self.frame_stack * O), dtype=torch.float32, device=dev)
-            nat.check(nat.lib.lz_evaluate_policy_attn_stack_f32(
-                self.env._h, ctypes.byref(e), self.frame_stack, _p(self.last_stack), _p(stack_out)))
-        elif self.attention:
-            nat.check(nat.lib.lz_evaluate_policy_attn_f32(self.env._h, ctypes.byref(e)))
+            stack = (self.frame_stack, _p(self.last_stack), _p(stack_out))
+            if tr is None:
+                nat.check(nat.lib.lz_evaluate_policy_attn_stack_f32(self.env._h, ctypes.byref(e), *stack))
+            else:
+                nat.check(nat.lib.lz_evaluate_policy_attn_stack_f32_trace(self.env._h, ctypes.byref(e), *stack,
+                                                                          ctypes.byref(tr)))
+        elif tr is None:
+            fn = nat.lib.lz_evaluate_policy_attn_f32 if self.attention else nat.lib.lz_evaluate_policy_f32
+            nat.check(fn(self.env._h, ctypes.byref(e)))
         else:
-            nat.check(nat.lib.lz_evaluate_policy_f32(self.env._h, ctypes.byref(e)))
+            fn = (nat.lib.lz_evaluate_policy_attn_f32_trace if self.attention
+                  else nat.lib.lz_evaluate_policy_f32_trace)
+            nat.check(fn(self.env._h, ctypes.byref(e), ctypes.byref(tr)))
         if es != caller:
             caller.wait_stream(es)
         self._keep = (self.blob, self.last_obs, self.last_stack)  # alive until consumed
         self.last_obs = obs_last
         if stack_out is not None:
             self.last_stack = stack_out
-        return EvalResult(stats, self.env.system_name)
+        if tr is None:
+            return EvalResult(stats, self.env.system_name)
+        self._keep += (ids_dev, trace_slot_map)
+        rows = EvalTrace(trace_out[:T * M * C].view(T, M, C), self.env.system_name, O, self.A,
+                         trace_state, trace_start, trace_every, ids_dev)
+        return EvalResult(stats, self.env.system_name, trace=rows)
 
 
 def evaluate_policy(backend, state_dict, n_eval_episodes, **kw):

@@ -62,6 +62,9 @@
  *          code/lorenz_filter/test_evaluate.py:94-157 (LayerNorm attention policy on
  *          VecFrameStack(4)), code/lorenz_pmsm/test_evaluate.py:61-166 (PMSM behind frozen
  *          VecNormalize) and SB3 evaluate_policy (code/gym_run.py:95)
+ *   lz_evaluate_policy_*_f32_trace (lz_eval_trace)
+ *       -> the per-step records those loops keep of chosen envs: the error and control
+ *          curves, the PMSM sheet's state1 - state2 columns, the master / slave states
  *
  * Conventions
  *   - Every function returns an lz_status (0 == LZ_OK).  Nothing throws across
@@ -658,6 +661,74 @@ lz_status lz_evaluate_policy_attn_f32(lz_handle* h, const lz_policy_eval_args* e
 lz_status lz_evaluate_policy_attn_stack_f32(lz_handle* h, const lz_policy_eval_args* e,
                                             int32_t n_stack, const float* stack_in,
                                             float* stack_out);
+
+/* ------------------------------------------------------------------------------
+ * Per-step trajectories of chosen envs in the fused evaluation.  Every one of the
+ * reference's evaluation loops also records the run it makes (code/test_evaluate.py:108-140
+ * err_x / err_y / err_z = obs[:3] * 50 and ctrl_x / ctrl_y = action * 100;
+ * code/lorenz_filter/test_evaluate.py:94-157; code/lorenz_pmsm/test_evaluate.py:113-134,
+ * 159-164 state1 - state2 of every step into PMSM_Origin_Data.xlsx; code/gym_run.py
+ * getResult and code/chaos_apl/main.py:1291-1294 the master / slave states).  The *_trace
+ * launches are the evaluation launches above -- the same [LZ_EVAL_COLS, N] table, state
+ * planes, obs_last, tick and call parity -- and write besides one time-major buffer
+ * out float32 [T, M, C]: a row per recorded step and chosen env.
+ *
+ * Recorded steps: step k (0 .. K-1) is recorded when k >= start and (k - start) % every
+ * == 0; it is row t = (k - start) / every, so T = ceil((K - start) / every).  every < 1,
+ * start < 0 and start >= K are LZ_ERR_INVALID.  skip and max_episodes do not affect the
+ * trace: uncounted steps are recorded too.
+ *
+ * Row [t, m, :] belongs to env ids[m]; C = O + A + 2, plus state_dim with LZ_TRACE_STATE:
+ *   [0, O)       o, the observation the step emitted before any auto-reset (the o of the
+ *                LZ_EVAL_* text above: the terminal observation on a done step); the
+ *                frame-stacked launch records this raw O-wide frame, not the stack
+ *   [O, O + A)   the clipped action the env was stepped with (what model.predict returns;
+ *                clip(sample) in a stochastic evaluation)
+ *   O + A        r, the float32 env reward, never bootstrapped
+ *   O + A + 1    the LZ_DONE_* bits as a float (0, 1, 2 or 3)
+ *   O + A + 2 .. with LZ_TRACE_STATE the system's state_dim leading state planes as held
+ *                after the step (after the reset on a step that auto-reset): what K single
+ *                lz_step calls, each followed by lz_get_state of planes 0 .. state_dim-1,
+ *                would read.  state_dim: LORENZ3 3, LORENZ4 8, PMSM 6, HR 6.
+ *
+ * ids is a device int64 [count] list, as lz_get_state takes.  Before the evaluation kernel
+ * the library builds, on the handle's stream, the device int32 [N] slot map (-1 everywhere,
+ * then slot_map[ids[m]] = m); a lane reads its env's slot whenever it opens a tile.  The
+ * map is the caller's buffer: nothing is allocated in a launch, which stays
+ * graph-capturable.  Ids outside [0, N) are skipped and their rows left unwritten.  For a
+ * repeated id it is unspecified which of its rows is written (gym_lorenz refuses them).
+ * count == 0 is the untraced launch.  A blob whose format tag does not match the launch
+ * gives an all-NaN trace, as it gives an all-NaN table.
+ * ------------------------------------------------------------------------------ */
+#define LZ_TRACE_STATE 1u /* append the state_dim leading state planes to every row */
+
+typedef struct lz_eval_trace {
+  const int64_t* ids;         /* device int64 [count] env ids */
+  int64_t count;              /* M >= 0 */
+  int32_t* slot_map;          /* device int32 [N] scratch, rebuilt by every traced launch */
+  int32_t start;              /* first recorded step, 0 <= start < K */
+  int32_t every;              /* stride in steps, >= 1 */
+  uint32_t flags;             /* LZ_TRACE_* */
+  float* out;                 /* device float32 [T, M, C] */
+  int64_t out_capacity_bytes; /* bytes out covers: >= T * M * C * 4 */
+} lz_eval_trace;
+
+/* rows = T and cols = C of a trace of K steps on a handle of cfg's system (host only: no
+ * device, no handle).  LZ_ERR_INVALID for K < 1, a bad start / every or unknown flags,
+ * LZ_ERR_UNSUPPORTED for a system the fused evaluation does not run. */
+lz_status lz_eval_trace_shape(const lz_config* cfg, int32_t K, int32_t start, int32_t every,
+                              uint32_t flags, int64_t* rows, int32_t* cols);
+
+/* The evaluation launches with a trace.  Refused (LZ_ERR_INVALID) besides everything the
+ * untraced entry refuses: NULL tr; count < 0; NULL ids / slot_map / out with count > 0;
+ * a bad start / every; unknown flags; out_capacity_bytes < T * M * C * 4. */
+lz_status lz_evaluate_policy_f32_trace(lz_handle* h, const lz_policy_eval_args* e,
+                                       const lz_eval_trace* tr);
+lz_status lz_evaluate_policy_attn_f32_trace(lz_handle* h, const lz_policy_eval_args* e,
+                                            const lz_eval_trace* tr);
+lz_status lz_evaluate_policy_attn_stack_f32_trace(lz_handle* h, const lz_policy_eval_args* e,
+                                                  int32_t n_stack, const float* stack_in,
+                                                  float* stack_out, const lz_eval_trace* tr);
 
 /* SB3 RolloutBuffer.compute_returns_and_advantage over time-major [K, N] float32
  * buffers (float32 arithmetic in NumPy's order): advantages and returns out.
