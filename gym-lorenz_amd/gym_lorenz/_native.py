@@ -173,6 +173,49 @@ class LzEvalTrace(ctypes.Structure):
 
 TRACE_STATE = 1  # LZ_TRACE_STATE
 
+
+class LzA2cGradArgs(ctypes.Structure):
+    """lz_a2c_grad_args (lz_a2c_grad_f32)."""
+    _fields_ = [
+        ("params", ctypes.c_void_p),
+        ("observations", ctypes.c_void_p),
+        ("actions", ctypes.c_void_p),
+        ("advantages", ctypes.c_void_p),
+        ("returns", ctypes.c_void_p),
+        ("n_samples", ctypes.c_int64),
+        ("obs_dim", ctypes.c_int32),
+        ("act_dim", ctypes.c_int32),
+        ("hidden", ctypes.c_int32),
+        ("max_workgroups", ctypes.c_int32),
+        ("vf_coef", ctypes.c_double),
+        ("ent_coef", ctypes.c_double),
+        ("workspace", ctypes.c_void_p),
+        ("workspace_bytes", ctypes.c_int64),
+        ("grad_sums", ctypes.c_void_p),
+    ]
+
+
+class LzA2cApplyArgs(ctypes.Structure):
+    """lz_a2c_apply_args (lz_a2c_apply_f32)."""
+    _fields_ = [
+        ("grad_sums", ctypes.c_void_p),
+        ("params", ctypes.c_void_p),
+        ("square_avg", ctypes.c_void_p),
+        ("n_params", ctypes.c_int64),
+        ("lr", ctypes.c_double),
+        ("max_grad_norm", ctypes.c_double),
+        ("alpha", ctypes.c_double),
+        ("eps", ctypes.c_double),
+        ("vf_coef", ctypes.c_double),
+        ("ent_coef", ctypes.c_double),
+        ("stats", ctypes.c_void_p),
+    ]
+
+
+# lz_a2c_apply_f32's stats double [8]
+A2C_STATS = ("policy_loss", "value_loss", "entropy_loss", "loss", "grad_norm", "clip_coef",
+             "n_samples", "lr")
+
 # columns of the evaluation table (lorenz_env.h LZ_EVAL_*): float64 [EVAL_COLS, N]
 (EVAL_ABS_SUM0, EVAL_SQ_SUM0, EVAL_MAX_ABS0) = 0, 4, 8
 (EVAL_N_WIN, EVAL_RET_SUM, EVAL_N_STEPS, EVAL_N_EP, EVAL_EP_RET_SUM, EVAL_EP_RET_SQ,
@@ -303,6 +346,11 @@ _SIGS = {
                                                                ctypes.POINTER(LzEvalTrace)]),
     "lz_gae": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, VP, VP, VP, VP, ctypes.c_double,
                               ctypes.c_double, VP, VP, ctypes.c_int32, VP]),
+    "lz_a2c_param_count": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
+    "lz_a2c_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_int32]),
+    "lz_a2c_grad_f32": (ctypes.c_int, [ctypes.POINTER(LzA2cGradArgs), ctypes.c_int32, VP]),
+    "lz_a2c_apply_f32": (ctypes.c_int, [ctypes.POINTER(LzA2cApplyArgs), ctypes.c_int32, VP]),
     "lz_episode_starts": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, VP, VP, VP, VP,
                                          ctypes.c_int32, VP]),
     "lz_frame_stack": (ctypes.c_int, [VP, VP, VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,

@@ -33,6 +33,10 @@ episode-return statistics kept as per-env float64 running sums on the device
 same launch also records those envs' per-step trajectories (``EvalTrace``: the scripts'
 error / control curves and state records).
 
+``FusedA2C.update(batch)`` is the learner's gradient step on such a batch (SB3
+``A2C.train()``: ``lz_a2c_grad_f32`` + ``lz_a2c_apply_f32``) and ``FusedA2C.learn`` the loop
+collect -> returns -> update of code/lorenz_pmsm/train.py:151-185, for the float32 MlpPolicy.
+
 ``ActorCriticMlp`` is a plain-torch restatement of SB3's ActorCriticPolicy for this
 net_arch (same state_dict keys, same orthogonal init) -- the weight source when SB3 is
 absent and the fp32 reference in the tests.  An SB3 policy's ``state_dict()`` can be
@@ -1170,3 +1174,208 @@ def evaluate_policy(backend, state_dict, n_eval_episodes, **kw):
     ev.reset()
     res = ev.evaluate(per_env * L, skip=0, max_episodes=per_env)
     return res.mean_reward, res.std_reward
+
+
+# ------------------------------------------------------------------------------ A2C update
+# SB3 2.7.1 A2C.train() for the float32 MlpPolicy on the device (lz_a2c_grad_f32 +
+# lz_a2c_apply_f32): the gradient step of code/lorenz_pmsm/train.py:151-185's learner.
+def linear_schedule(initial_value):
+    """code/lorenz_pmsm/train.py:187-197: the learning rate falls linearly with SB3's
+    ``progress_remaining`` (1 -> 0) and never below 1e-5."""
+    initial_value = float(initial_value)
+
+    def schedule(progress_remaining):
+        return max(progress_remaining * initial_value, 1e-5)
+
+    return schedule
+
+
+def a2c_param_shapes(obs_dim, act_dim):
+    """The 13 tensors' shapes in KEYS order (nn.Linear layout)."""
+    H = HIDDEN
+    return [(H, obs_dim), (H,), (H, H), (H,)] * 2 + [(act_dim, H), (act_dim,), (1, H), (1,),
+                                                      (act_dim,)]
+
+
+def a2c_param_layout(obs_dim, act_dim):
+    """{key: (offset, shape)} of lz_a2c_grad_f32's flat parameter vector, and its length."""
+    out, o = {}, 0
+    for k, shp in zip(KEYS, a2c_param_shapes(obs_dim, act_dim)):
+        out[k] = (o, shp)
+        o += int(np.prod(shp))
+    return out, o
+
+
+def a2c_grad(params, observations, actions, advantages, returns, obs_dim, act_dim, vf_coef=0.5,
+             ent_coef=0.0, max_workgroups=0, workspace=None, out=None, hidden=HIDDEN):
+    """lz_a2c_grad_f32 on the current stream: float64 device tensor [P + 4] of gradient sums
+    over the samples, then sum(-adv log_prob), sum((ret - v)^2), sum(-entropy), the count.
+    Every buffer is checked (core.check_buffer) before the launch."""
+    dev = params.device
+    O, A = int(obs_dim), int(act_dim)
+    if dev.type != "cuda":
+        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "a2c_grad: params must be a device tensor")
+    P = int(nat.lib.lz_a2c_param_count(O, A))
+    if P < 0:
+        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "a2c_grad: obs_dim must be 1..8, act_dim 1..4")
+    B = int(advantages.numel())
+    f32 = torch.float32
+    g = nat.LzA2cGradArgs()
+    g.params = check_buffer(params, "params", f32, P, dev)
+    g.observations = check_buffer(observations, "observations", f32, B * O, dev)
+    g.actions = check_buffer(actions, "actions", f32, B * A, dev)
+    g.advantages = check_buffer(advantages, "advantages", f32, B, dev)
+    g.returns = check_buffer(returns, "returns", f32, B, dev)
+    g.n_samples, g.obs_dim, g.act_dim, g.hidden = B, O, A, int(hidden)
+    g.max_workgroups = int(max_workgroups)
+    g.vf_coef, g.ent_coef = float(vf_coef), float(ent_coef)
+    need = int(nat.lib.lz_a2c_workspace_bytes(B, O, A, int(max_workgroups)))
+    if need < 0:
+        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "a2c_grad: empty batch or bad max_workgroups")
+    if workspace is None:
+        workspace = torch.empty((need // 8,), dtype=torch.float64, device=dev)
+    g.workspace = check_buffer(workspace, "workspace", torch.float64, need // 8, dev, at_least=True)
+    g.workspace_bytes = workspace.numel() * 8
+    if out is None:
+        out = torch.empty((P + 4,), dtype=torch.float64, device=dev)
+    g.grad_sums = check_buffer(out, "grad_sums", torch.float64, P + 4, dev)
+    nat.check(nat.lib.lz_a2c_grad_f32(ctypes.byref(g), dev.index,
+                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return out
+
+
+def a2c_apply(grad_sums, params, square_avg, lr, max_grad_norm=0.5, alpha=0.99, eps=1e-5,
+              vf_coef=0.5, ent_coef=0.0, stats=None):
+    """lz_a2c_apply_f32 on the current stream: clip_grad_norm_ + the RMSpropTFLike step on
+    params / square_avg in place; returns the float64 device tensor stats [8]
+    (_native.A2C_STATS)."""
+    dev = params.device
+    if dev.type != "cuda":
+        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "a2c_apply: params must be a device tensor")
+    P = int(params.numel())
+    a = nat.LzA2cApplyArgs()
+    a.grad_sums = check_buffer(grad_sums, "grad_sums", torch.float64, P + 4, dev)
+    a.params = check_buffer(params, "params", torch.float32, P, dev)
+    a.square_avg = check_buffer(square_avg, "square_avg", torch.float32, P, dev)
+    a.n_params = P
+    a.lr, a.max_grad_norm, a.alpha, a.eps = float(lr), float(max_grad_norm), float(alpha), float(eps)
+    a.vf_coef, a.ent_coef = float(vf_coef), float(ent_coef)
+    if stats is None:
+        stats = torch.empty((8,), dtype=torch.float64, device=dev)
+    a.stats = check_buffer(stats, "stats", torch.float64, 8, dev)
+    nat.check(nat.lib.lz_a2c_apply_f32(ctypes.byref(a), dev.index,
+                                       ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return stats
+
+
+class FusedA2C:
+    """SB3 A2C on a FusedRolloutCollector: ``learn`` is the loop collect(n_steps) ->
+    compute_returns_and_advantage -> update, and ``update`` one A2C.train() -- the whole
+    rollout as one batch, loss = -mean(adv log_prob) + vf_coef mse(returns, values) +
+    ent_coef (-mean(entropy)), clip_grad_norm_(max_grad_norm), RMSpropTFLike(alpha=0.99,
+    eps=rms_prop_eps) -- in two launches (lz_a2c_grad_f32, lz_a2c_apply_f32) with, when
+    ``group`` is set, an all-reduce of the [P + 4] gradient sums between them.  The
+    parameters live on the device as one flat float32 vector; after each step they go
+    through the host packer into the collector's blob (collector.set_params).
+
+    learning_rate: a float or a schedule of SB3's progress_remaining (linear_schedule).
+    Float32 MlpPolicy collectors only; normalize_advantage and Adam are not implemented."""
+
+    def __init__(self, collector, state_dict, learning_rate=7e-4, n_steps=5, vf_coef=0.5,
+                 ent_coef=0.0, max_grad_norm=0.5, rms_prop_eps=1e-5, group=None,
+                 normalize_advantage=False, use_rms_prop=True):
+        if normalize_advantage:
+            raise ValueError("FusedA2C: normalize_advantage is not implemented (SB3's default-off "
+                             "option; the reference leaves it off)")
+        if not use_rms_prop:
+            raise ValueError("FusedA2C: only RMSpropTFLike (use_rms_prop=True) is implemented")
+        if is_attention_policy(state_dict) or is_attention_ln_policy(state_dict):
+            raise ValueError("FusedA2C updates the MlpPolicy; the attention policies' update is "
+                             "not implemented")
+        if collector.precision in ("bf16", "i8x4"):
+            raise ValueError("FusedA2C needs a float32 collector (precision='fp32'), not %r"
+                             % collector.precision)
+        if collector.frame_stack != 1:
+            raise ValueError("FusedA2C updates the MlpPolicy (frame_stack=1)")
+        self.collector = collector
+        self.device = collector.device
+        self.O, self.A = collector.O, collector.A
+        self.layout, self.P = a2c_param_layout(self.O, self.A)
+        flat = []
+        for k, (_, shp) in self.layout.items():
+            if k not in state_dict:
+                raise KeyError("policy state_dict lacks %r" % k)
+            t = torch.as_tensor(_np(state_dict[k]))
+            if tuple(t.shape) != tuple(shp):
+                raise ValueError("%s has shape %s, expected %s (FusedA2C implements hidden=%d)"
+                                 % (k, tuple(t.shape), shp, HIDDEN))
+            flat.append(t.reshape(-1))
+        self.params = torch.cat(flat).to(self.device).contiguous()
+        self.square_avg = torch.ones_like(self.params)  # RMSpropTFLike starts at ones
+        self.learning_rate = learning_rate
+        self.n_steps = int(n_steps)
+        self.vf_coef, self.ent_coef = float(vf_coef), float(ent_coef)
+        self.max_grad_norm, self.rms_prop_eps = float(max_grad_norm), float(rms_prop_eps)
+        self.group = group
+        self.num_timesteps = 0
+        self.progress_remaining = 1.0
+        self._sums = torch.empty((self.P + 4,), dtype=torch.float64, device=self.device)
+        self._ws = None
+        collector.set_params(self.state_dict())
+
+    def _lr(self):
+        lr = self.learning_rate
+        return float(lr(self.progress_remaining)) if callable(lr) else float(lr)
+
+    def state_dict(self):
+        """SB3 keys -> float32 CPU tensors (one device-to-host copy)."""
+        flat = self.params.detach().cpu()
+        return {k: flat[o:o + int(np.prod(shp))].reshape(shp).clone()
+                for k, (o, shp) in self.layout.items()}
+
+    def optimizer_state(self):
+        """{"square_avg": {SB3 key: float32 CPU tensor}}: RMSpropTFLike's state."""
+        flat = self.square_avg.detach().cpu()
+        return {"square_avg": {k: flat[o:o + int(np.prod(shp))].reshape(shp).clone()
+                               for k, (o, shp) in self.layout.items()}}
+
+    def update(self, batch, lr=None):
+        """One gradient step on the whole RolloutBatch (advantages / returns set by
+        compute_returns_and_advantage); pushes the new weights to the collector.  Returns
+        the stats as a dict of Python floats (_native.A2C_STATS)."""
+        if batch.advantages is None or batch.returns is None:
+            raise ValueError("FusedA2C.update: compute_returns_and_advantage(batch) first")
+        lr = self._lr() if lr is None else float(lr)
+        B = int(batch.advantages.numel())
+        need = int(nat.lib.lz_a2c_workspace_bytes(B, self.O, self.A, 0)) // 8
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty((max(need, 1),), dtype=torch.float64, device=self.device)
+        a2c_grad(self.params, batch.observations, batch.actions, batch.advantages, batch.returns,
+                 self.O, self.A, self.vf_coef, self.ent_coef, workspace=self._ws, out=self._sums)
+        if self.group is not None:
+            dist.all_reduce(self._sums, group=self.group)
+        stats = a2c_apply(self._sums, self.params, self.square_avg, lr, self.max_grad_norm, 0.99,
+                          self.rms_prop_eps, self.vf_coef, self.ent_coef)
+        self.collector.set_params(self.state_dict())
+        return dict(zip(nat.A2C_STATS, stats.cpu().tolist()))
+
+    def learn(self, total_timesteps, callback=None):
+        """SB3 OnPolicyAlgorithm.learn: rollouts of n_steps x num_envs timesteps until
+        total_timesteps, progress_remaining = 1 - num_timesteps / total_timesteps updated
+        after each collect (what the schedule sees in train()).  callback(self, batch, stats)
+        runs after every update.  Returns the list of the updates' stats."""
+        total = int(total_timesteps)
+        col = self.collector
+        n = col.n * (dist.get_world_size(self.group) if self.group is not None else 1)
+        out = []
+        start = self.num_timesteps
+        while self.num_timesteps - start < total:
+            batch = col.collect(self.n_steps)
+            self.num_timesteps += self.n_steps * n
+            self.progress_remaining = 1.0 - float(self.num_timesteps - start) / float(total)
+            col.compute_returns_and_advantage(batch)
+            stats = self.update(batch)
+            out.append(stats)
+            if callback is not None:
+                callback(self, batch, stats)
+        return out

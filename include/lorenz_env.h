@@ -47,6 +47,9 @@
  *          advantage for the MlpPolicy learners (code/lorenz_pmsm/train.py:155-178,
  *          optimize.py:36-60 ([64,64] / [128,128]), code/gym_run.py:83 (PPO default
  *          net_arch [64,64]))
+ *   lz_a2c_grad_f32 / lz_a2c_apply_f32 (lz_a2c_workspace_bytes, lz_a2c_param_count)
+ *       -> SB3 A2C.train() for those MlpPolicy learners: one gradient step on the whole
+ *          rollout, clip_grad_norm_ and RMSpropTFLike (code/lorenz_pmsm/train.py:151-185)
  *   lz_attn_policy_pack / lz_rollout_policy_attn
  *       -> the same for code/train.py:52-112 and code/gym_try.py:52-116 (PPO with the
  *          AttentionFeaturesExtractor)
@@ -737,6 +740,82 @@ lz_status lz_gae(int64_t n, int32_t K, const float* rew, const float* values,
                  const uint8_t* done, const float* last_values, double gamma,
                  double gae_lambda, float* advantages, float* returns, int32_t device,
                  void* hip_stream);
+
+/* ------------------------------------------------------------------------------
+ * One A2C gradient step for the float32 MlpPolicy (pi = vf = [128, 128], Tanh) on a rollout
+ * batch that is already on the device: SB3 2.7.1 A2C.train() (a2c/a2c.py:134-190) as the
+ * reference's learner runs it (code/lorenz_pmsm/train.py:151-185: A2C, n_steps=16,
+ * max_grad_norm=0.5, RMSpropTFLike, a linear learning-rate schedule).  All B = K*N rows of
+ * the rollout in one batch; with mu the pi net's head, v the vf net's, sigma = exp(log_std):
+ *   log_prob = sum_a [ -(a - mu)^2 / (2 sigma^2) - log sigma - log(2 pi)/2 ]
+ *   entropy  = sum_a [ 1/2 + log(2 pi)/2 + log sigma ]       (common/distributions.py)
+ *   loss     = -mean(adv log_prob) + vf_coef mean((ret - v)^2) + ent_coef (-mean(entropy))
+ * (normalize_advantage is not implemented: SB3's default-off option.)
+ *
+ * params is the flat float32 vector of the 13 tensors in the order of lz_mlp_policy's
+ * pointer fields' SB3 keys -- policy_net.0.weight [128, O], .0.bias, .2.weight [128, 128],
+ * .2.bias, value_net.0.weight, .0.bias, .2.weight, .2.bias, action_net.weight [A, 128],
+ * action_net.bias, value_net.weight [1, 128], value_net.bias, log_std [A] -- each in
+ * nn.Linear layout; P = lz_a2c_param_count(O, A) floats (35,205 at O = 6, A = 2).
+ *
+ * lz_a2c_grad_f32 writes grad_sums double [P + 4]: entries 0 .. P-1 the SUM over the
+ * samples of the per-sample loss gradient (not divided by B), then sum(-adv log_prob),
+ * sum((ret - v)^2), sum(-entropy) and the sample count.  A multi-GPU learner all-reduces
+ * this vector (SUM) between the two calls.  Float32 forward and backward (f32-input MFMA,
+ * float32-accurate tanh), float32 sums over at most 2048 samples, float64 above that; every
+ * workgroup adds into its own slot of the caller's workspace and a second kernel adds the
+ * slots in a fixed order: no atomics, the same bits from the same inputs.  NaN / inf inputs
+ * propagate as they would in torch.  Two kernels, no allocation, no host synchronisation:
+ * graph-capturable.  Refused before any HIP call: NULL pointers, obs_dim outside 1..8,
+ * act_dim outside 1..4, n_samples < 1, max_workgroups outside 0..4096, a workspace smaller
+ * than lz_a2c_workspace_bytes (LZ_ERR_INVALID); hidden != 128 (LZ_ERR_UNSUPPORTED).
+ *
+ * lz_a2c_apply_f32 takes grad_sums and, in float64 throughout:
+ *   g = float32(grad_sums[i] / count)               (what torch's .grad would hold)
+ *   total = ||g||_2;  coef = min(1, max_grad_norm / (total + 1e-6))     (clip_grad_norm_)
+ *   s = alpha square_avg + (1 - alpha) (coef g)^2;  p = p - lr coef g / sqrt(s + eps)
+ * (RMSpropTFLike, common/sb2_compat/rmsprop_tf_like.py: no momentum, not centred, no weight
+ * decay, eps inside the root; the caller initialises square_avg to ONES), rounding s and p
+ * once into the float32 square_avg and params, in place.  stats double [8]: policy loss,
+ * value loss, entropy loss, loss, gradient norm before clipping, clip coefficient, sample
+ * count, lr.
+ * ------------------------------------------------------------------------------ */
+typedef struct lz_a2c_grad_args {
+  const float* params;        /* [P] */
+  const float* observations;  /* [B, O] as the policy saw them (RolloutBatch.observations) */
+  const float* actions;       /* [B, A] the unclipped samples */
+  const float* advantages;    /* [B] */
+  const float* returns;       /* [B] */
+  int64_t n_samples;          /* B >= 1 */
+  int32_t obs_dim;            /* 1..8 */
+  int32_t act_dim;            /* 1..4 */
+  int32_t hidden;             /* 128 */
+  int32_t max_workgroups;     /* cap on the workgroups per net (tests: forces the grid-stride
+                                 loop at small B); 0 = the default, 128 */
+  double vf_coef, ent_coef;
+  void* workspace;            /* device, >= lz_a2c_workspace_bytes(...) bytes */
+  int64_t workspace_bytes;
+  double* grad_sums;          /* [P + 4] out */
+} lz_a2c_grad_args;
+
+typedef struct lz_a2c_apply_args {
+  const double* grad_sums;    /* [P + 4] */
+  float* params;              /* [P] in place */
+  float* square_avg;          /* [P] in place */
+  int64_t n_params;           /* P */
+  double lr, max_grad_norm, alpha, eps;
+  double vf_coef, ent_coef;   /* for stats[3] only */
+  double* stats;              /* [8] out */
+} lz_a2c_apply_args;
+
+/* P for (obs_dim, act_dim), -1 if they are out of range.  Host-only. */
+int64_t lz_a2c_param_count(int32_t obs_dim, int32_t act_dim);
+/* The workspace bytes a lz_a2c_grad_f32 call with these arguments needs, -1 if it would
+ * refuse them.  Host-only. */
+int64_t lz_a2c_workspace_bytes(int64_t n_samples, int32_t obs_dim, int32_t act_dim,
+                               int32_t max_workgroups);
+lz_status lz_a2c_grad_f32(const lz_a2c_grad_args* g, int32_t device, void* hip_stream);
+lz_status lz_a2c_apply_f32(const lz_a2c_apply_args* a, int32_t device, void* hip_stream);
 
 /* RolloutBuffer.episode_starts of one collect (SB3 2.7.1 OnPolicyAlgorithm.
  * collect_rollouts: rollout_buffer.add(..., self._last_episode_starts, ...), then
