@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 #include "lz_internal.h"
@@ -499,8 +500,89 @@ void pack_gauss(float* ls, int act_dim, const float* log_std) {
   }
 }
 
-lz_status pfail(lz_status s, const char* msg) {
-  return lz::set_error(s, msg);
+lz_status pfail(lz_status s, const char* msg) { return lz::set_error(s, msg); }
+
+// The entry points' refusals, each written once; every entry point runs them in its own
+// order (which of two violations wins is part of its contract).
+lz_status check_blob(const void* p, const void* host_blob, int64_t cap, int64_t need) {
+  if (!p || !host_blob) return pfail(LZ_ERR_INVALID, "policy/blob is NULL");
+  if (cap < need) return pfail(LZ_ERR_INVALID, "blob capacity too small");
+  return LZ_OK;
+}
+lz_status check_hidden(int32_t hidden) {
+  if (hidden < 1 || hidden > lz::kPolHidden) return pfail(LZ_ERR_UNSUPPORTED, "hidden width must be 1..128");
+  return LZ_OK;
+}
+// max_in: kPolMaxObs for the raw-observation policies, else the stacked input width
+lz_status check_dims(int obs_dim, int act_dim, int max_in) {
+  if (obs_dim < 1 || obs_dim > max_in || act_dim < 1 || act_dim > lz::kPolMaxAct)
+    return pfail(LZ_ERR_UNSUPPORTED, max_in == lz::kPolMaxObs
+                                         ? "policy supports obs_dim 1..8 and act_dim 1..4"
+                                         : "policy supports input dims 1..32 and act_dim 1..4");
+  return LZ_OK;
+}
+lz_status check_ptrs(std::initializer_list<const float*> req) {
+  for (const float* q : req)
+    if (!q) return pfail(LZ_ERR_INVALID, "a policy weight pointer is NULL");
+  return LZ_OK;
+}
+lz_status check_mlp_ptrs(const lz_mlp_policy* p) {
+  return check_ptrs({p->pi_w1, p->pi_b1, p->pi_w2, p->pi_b2, p->vf_w1, p->vf_b1, p->vf_w2, p->vf_b2,
+                     p->act_w, p->act_b, p->val_w, p->val_b, p->log_std});
+}
+// the attention list, then (ln given) the LayerNorm pair
+lz_status check_attn_ptrs(const lz_attn_policy* p, const lz_attn_ln_policy* ln = nullptr) {
+  if (lz_status s = check_ptrs({p->fc1_w, p->fc1_b, p->in_proj_w, p->in_proj_b, p->out_proj_w,
+                                p->out_proj_b, p->post_w, p->post_b, p->pi_w1, p->pi_b1, p->pi_w2,
+                                p->pi_b2, p->vf_w1, p->vf_b1, p->vf_w2, p->vf_b2, p->act_w, p->act_b,
+                                p->val_w, p->val_b, p->log_std}))
+    return s;
+  return ln ? check_ptrs({ln->ln_w, ln->ln_b}) : LZ_OK;
+}
+// the float32 / i8x4 LayerNorm entry points look at their own struct before anything else
+lz_status check_ln(const lz_attn_ln_policy* p) {
+  if (!p) return pfail(LZ_ERR_INVALID, "policy is NULL");
+  if (!p->ln_w || !p->ln_b) return pfail(LZ_ERR_INVALID, "layer_norm weight / bias is NULL");
+  return LZ_OK;
+}
+
+// A [hidden, hidden] MlpPolicy zero-padded to the kernels' 128 units (w points into buf):
+// a padded unit's pre-activation is exactly 0, tanh(0) = 0, and its zero weights add exact
+// zeros downstream (fma(0, w, acc) = acc) -- the kernels compute the narrower net unchanged
+struct PaddedMlp {
+  std::vector<float> buf;
+  lz_mlp_policy w;
+};
+PaddedMlp pad_to_hidden(const lz_mlp_policy* p, int hidden) {
+  const int H = lz::kPolHidden, O = p->obs_dim, A = p->act_dim;
+  PaddedMlp out{std::vector<float>((size_t)2 * (H * O + H + H * H + H) + (size_t)(A + 1) * H, 0.0f), *p};
+  float* q = out.buf.data();
+  auto pad = [&](const float* src, int rows, int cols, int prow, int pcol) {
+    float* dst = q;
+    for (int r = 0; r < rows; ++r)
+      for (int c = 0; c < cols; ++c) dst[r * pcol + c] = src[r * cols + c];
+    q += (size_t)prow * pcol;
+    return dst;
+  };
+  lz_mlp_policy& w = out.w;
+  w.pi_w1 = pad(p->pi_w1, hidden, O, H, O);
+  w.pi_b1 = pad(p->pi_b1, 1, hidden, 1, H);
+  w.pi_w2 = pad(p->pi_w2, hidden, hidden, H, H);
+  w.pi_b2 = pad(p->pi_b2, 1, hidden, 1, H);
+  w.vf_w1 = pad(p->vf_w1, hidden, O, H, O);
+  w.vf_b1 = pad(p->vf_b1, 1, hidden, 1, H);
+  w.vf_w2 = pad(p->vf_w2, hidden, hidden, H, H);
+  w.vf_b2 = pad(p->vf_b2, 1, hidden, 1, H);
+  w.act_w = pad(p->act_w, A, hidden, A, H);
+  w.val_w = pad(p->val_w, 1, hidden, 1, H);
+  return out;
+}
+
+// kF32Tanh / kAFTanh: c_j 8^-j, the kernel's Horner runs in u = 8 t (tanh_tab)
+void write_tanh_table(float* tt) {
+  for (int k = 0; k < 72; ++k)
+    for (int j = 0; j < 8; ++j) tt[8 * k + j] = std::ldexp(kTanhTab[8 * k + j], -3 * j);
+  tt[8 * 72] = 1.0f;  // segment 72: the constant 1 (the rest stays zero)
 }
 
 }  // namespace
@@ -510,14 +592,9 @@ extern "C" {
 int64_t lz_policy_blob_bytes(void) { return lz::kPolBlobBytes; }
 
 lz_status lz_policy_pack(const lz_mlp_policy* p, void* host_blob, int64_t cap) {
-  if (!p || !host_blob) return pfail(LZ_ERR_INVALID, "policy/blob is NULL");
-  if (cap < lz::kPolBlobBytes) return pfail(LZ_ERR_INVALID, "blob capacity too small");
-  if (p->obs_dim < 1 || p->obs_dim > lz::kPolMaxObs || p->act_dim < 1 || p->act_dim > lz::kPolMaxAct)
-    return pfail(LZ_ERR_UNSUPPORTED, "policy supports obs_dim 1..8 and act_dim 1..4");
-  const float* req[] = {p->pi_w1, p->pi_b1, p->pi_w2, p->pi_b2, p->vf_w1, p->vf_b1, p->vf_w2,
-                        p->vf_b2, p->act_w, p->act_b, p->val_w, p->val_b, p->log_std};
-  for (const float* q : req)
-    if (!q) return pfail(LZ_ERR_INVALID, "a policy weight pointer is NULL");
+  if (lz_status s = check_blob(p, host_blob, cap, lz::kPolBlobBytes)) return s;
+  if (lz_status s = check_dims(p->obs_dim, p->act_dim, lz::kPolMaxObs)) return s;
+  if (lz_status s = check_mlp_ptrs(p)) return s;
   uint8_t* b = static_cast<uint8_t*>(host_blob);
   std::memset(b, 0, lz::kPolBlobBytes);
   pack_net(b, p->obs_dim, p->act_dim, p->pi_w1, p->pi_b1, p->pi_w2, p->pi_b2, p->act_w, p->act_b);
@@ -529,41 +606,14 @@ lz_status lz_policy_pack(const lz_mlp_policy* p, void* host_blob, int64_t cap) {
 
 lz_status lz_policy_pack_hidden(const lz_mlp_policy* p, int32_t hidden, void* host_blob,
                                 int64_t cap) {
-  // a [hidden, hidden] net zero-padded to 128 units: a padded unit's pre-activation is
-  // exactly 0, tanh(0) = 0, and its zero weights add exact zeros downstream -- the
-  // 128-wide kernel computes the narrower net unchanged
+  // a narrower net: dims and pointers are looked at before the blob (in lz_policy_pack)
   if (!p) return pfail(LZ_ERR_INVALID, "policy is NULL");
   if (hidden == lz::kPolHidden) return lz_policy_pack(p, host_blob, cap);
-  if (hidden < 1 || hidden > lz::kPolHidden)
-    return pfail(LZ_ERR_UNSUPPORTED, "hidden width must be 1..128");
-  if (p->obs_dim < 1 || p->obs_dim > lz::kPolMaxObs || p->act_dim < 1 || p->act_dim > lz::kPolMaxAct)
-    return pfail(LZ_ERR_UNSUPPORTED, "policy supports obs_dim 1..8 and act_dim 1..4");
-  const float* req[] = {p->pi_w1, p->pi_b1, p->pi_w2, p->pi_b2, p->vf_w1, p->vf_b1, p->vf_w2,
-                        p->vf_b2, p->act_w, p->act_b, p->val_w, p->val_b, p->log_std};
-  for (const float* q : req)
-    if (!q) return pfail(LZ_ERR_INVALID, "a policy weight pointer is NULL");
-  const int H = lz::kPolHidden, O = p->obs_dim, A = p->act_dim;
-  std::vector<float> buf((size_t)2 * (H * O + H + H * H + H) + (size_t)(A + 1) * H, 0.0f);
-  float* q = buf.data();
-  auto pad = [&](const float* src, int rows, int cols, int prow, int pcol) {
-    float* dst = q;
-    for (int r = 0; r < rows; ++r)
-      for (int c = 0; c < cols; ++c) dst[r * pcol + c] = src[r * cols + c];
-    q += (size_t)prow * pcol;
-    return dst;
-  };
-  lz_mlp_policy w = *p;
-  w.pi_w1 = pad(p->pi_w1, hidden, O, H, O);
-  w.pi_b1 = pad(p->pi_b1, 1, hidden, 1, H);
-  w.pi_w2 = pad(p->pi_w2, hidden, hidden, H, H);
-  w.pi_b2 = pad(p->pi_b2, 1, hidden, 1, H);
-  w.vf_w1 = pad(p->vf_w1, hidden, O, H, O);
-  w.vf_b1 = pad(p->vf_b1, 1, hidden, 1, H);
-  w.vf_w2 = pad(p->vf_w2, hidden, hidden, H, H);
-  w.vf_b2 = pad(p->vf_b2, 1, hidden, 1, H);
-  w.act_w = pad(p->act_w, A, hidden, A, H);
-  w.val_w = pad(p->val_w, 1, hidden, 1, H);
-  return lz_policy_pack(&w, host_blob, cap);
+  if (lz_status s = check_hidden(hidden)) return s;
+  if (lz_status s = check_dims(p->obs_dim, p->act_dim, lz::kPolMaxObs)) return s;
+  if (lz_status s = check_mlp_ptrs(p)) return s;
+  const PaddedMlp padded = pad_to_hidden(p, hidden);
+  return lz_policy_pack(&padded.w, host_blob, cap);
 }
 
 int64_t lz_policy_f32_blob_bytes(void) { return lz::kF32BlobBytes; }
@@ -592,7 +642,32 @@ static void pack_net_i8x4(uint8_t* net, const float* w2) {
       for (int g = 0; g < 16; ++g) sh[(2 * T + h) * 16 + g] = (int16_t)(24 - q[32 * T + row_of(g, h)] - 28);
 }
 
-static lz_status pack_mlp_f32(const lz_mlp_policy* p, int32_t hidden, void* host_blob, int64_t cap, bool i8);
+static lz_status pack_mlp_f32(const lz_mlp_policy* p, int32_t hidden, void* host_blob, int64_t cap, bool i8) {
+  if (lz_status s = check_blob(p, host_blob, cap, lz::kF32BlobBytes)) return s;
+  if (lz_status s = check_hidden(hidden)) return s;
+  if (lz_status s = check_dims(p->obs_dim, p->act_dim, lz::kPolMaxObs)) return s;
+  if (lz_status s = check_mlp_ptrs(p)) return s;
+  const PaddedMlp padded = pad_to_hidden(p, hidden);
+  const lz_mlp_policy& w = padded.w;
+  const int H = lz::kPolHidden, O = p->obs_dim, A = p->act_dim;
+  uint8_t* b = static_cast<uint8_t*>(host_blob);
+  std::memset(b, 0, lz::kF32BlobBytes);
+  if (i8) {
+    for (const float* w2 : {w.pi_w2, w.vf_w2})
+      for (int k = 0; k < H * H; ++k)
+        if (!std::isfinite(w2[k])) return pfail(LZ_ERR_INVALID, "i8x4: layer 2 weights must be finite");
+  }
+  pack_net_f32(b, O, A, w.pi_w1, w.pi_b1, w.pi_w2, w.pi_b2, w.act_w, w.act_b);
+  pack_net_f32(b + lz::kF32Net, O, 1, w.vf_w1, w.vf_b1, w.vf_w2, w.vf_b2, w.val_w, w.val_b);
+  if (i8) {
+    pack_net_i8x4(b, w.pi_w2);
+    pack_net_i8x4(b + lz::kF32Net, w.vf_w2);
+  }
+  pack_gauss(reinterpret_cast<float*>(b + lz::kF32LogStd), A, w.log_std);
+  lz::blob_tag(i8 ? LZ_BLOB_MLP_I8X4 : LZ_BLOB_MLP_F32, reinterpret_cast<uint32_t*>(b + lz::kF32Tag));
+  write_tanh_table(reinterpret_cast<float*>(b + lz::kF32Tanh));
+  return LZ_OK;
+}
 
 lz_status lz_policy_pack_f32(const lz_mlp_policy* p, int32_t hidden, void* host_blob, int64_t cap) {
   return pack_mlp_f32(p, hidden, host_blob, cap, false);
@@ -602,75 +677,12 @@ lz_status lz_policy_pack_i8x4(const lz_mlp_policy* p, int32_t hidden, void* host
   return pack_mlp_f32(p, hidden, host_blob, cap, true);
 }
 
-static lz_status pack_mlp_f32(const lz_mlp_policy* p, int32_t hidden, void* host_blob, int64_t cap, bool i8) {
-  if (!p || !host_blob) return pfail(LZ_ERR_INVALID, "policy/blob is NULL");
-  if (cap < lz::kF32BlobBytes) return pfail(LZ_ERR_INVALID, "blob capacity too small");
-  if (hidden < 1 || hidden > lz::kPolHidden) return pfail(LZ_ERR_UNSUPPORTED, "hidden width must be 1..128");
-  if (p->obs_dim < 1 || p->obs_dim > lz::kPolMaxObs || p->act_dim < 1 || p->act_dim > lz::kPolMaxAct)
-    return pfail(LZ_ERR_UNSUPPORTED, "policy supports obs_dim 1..8 and act_dim 1..4");
-  const float* req[] = {p->pi_w1, p->pi_b1, p->pi_w2, p->pi_b2, p->vf_w1, p->vf_b1, p->vf_w2,
-                        p->vf_b2, p->act_w, p->act_b, p->val_w, p->val_b, p->log_std};
-  for (const float* q : req)
-    if (!q) return pfail(LZ_ERR_INVALID, "a policy weight pointer is NULL");
-  // zero-pad a [hidden, hidden] net to the kernel's 128 units (as lz_policy_pack_hidden):
-  // a padded unit is tanh(0) = 0 with zero weights, each of its chain steps fma(0, w, acc)
-  // returns acc unchanged
-  const int H = lz::kPolHidden, O = p->obs_dim, A = p->act_dim;
-  std::vector<float> buf((size_t)2 * (H * O + H + H * H + H) + (size_t)(A + 1) * H, 0.0f);
-  float* q = buf.data();
-  auto pad = [&](const float* src, int rows, int cols, int prow, int pcol) {
-    float* dst = q;
-    for (int r = 0; r < rows; ++r)
-      for (int c = 0; c < cols; ++c) dst[r * pcol + c] = src[r * cols + c];
-    q += (size_t)prow * pcol;
-    return dst;
-  };
-  const float* pw1 = pad(p->pi_w1, hidden, O, H, O);
-  const float* pb1 = pad(p->pi_b1, 1, hidden, 1, H);
-  const float* pw2 = pad(p->pi_w2, hidden, hidden, H, H);
-  const float* pb2 = pad(p->pi_b2, 1, hidden, 1, H);
-  const float* vw1 = pad(p->vf_w1, hidden, O, H, O);
-  const float* vb1 = pad(p->vf_b1, 1, hidden, 1, H);
-  const float* vw2 = pad(p->vf_w2, hidden, hidden, H, H);
-  const float* vb2 = pad(p->vf_b2, 1, hidden, 1, H);
-  const float* aw = pad(p->act_w, A, hidden, A, H);
-  const float* uw = pad(p->val_w, 1, hidden, 1, H);
-  uint8_t* b = static_cast<uint8_t*>(host_blob);
-  std::memset(b, 0, lz::kF32BlobBytes);
-  if (i8) {
-    for (const float* w : {pw2, vw2})
-      for (int k = 0; k < H * H; ++k)
-        if (!std::isfinite(w[k])) return pfail(LZ_ERR_INVALID, "i8x4: layer 2 weights must be finite");
-  }
-  pack_net_f32(b, O, A, pw1, pb1, pw2, pb2, aw, p->act_b);
-  pack_net_f32(b + lz::kF32Net, O, 1, vw1, vb1, vw2, vb2, uw, p->val_b);
-  if (i8) {
-    pack_net_i8x4(b, pw2);
-    pack_net_i8x4(b + lz::kF32Net, vw2);
-  }
-  pack_gauss(reinterpret_cast<float*>(b + lz::kF32LogStd), A, p->log_std);
-  lz::blob_tag(i8 ? LZ_BLOB_MLP_I8X4 : LZ_BLOB_MLP_F32, reinterpret_cast<uint32_t*>(b + lz::kF32Tag));
-  // c_j 8^-j: the kernel's Horner runs in u = 8 t (tanh_tab)
-  float* tt = reinterpret_cast<float*>(b + lz::kF32Tanh);
-  for (int k = 0; k < 72; ++k)
-    for (int j = 0; j < 8; ++j) tt[8 * k + j] = std::ldexp(kTanhTab[8 * k + j], -3 * j);
-  tt[8 * 72] = 1.0f;  // segment 72: the constant 1 (the rest stays zero)
-  return LZ_OK;
-}
-
 int64_t lz_attn_policy_blob_bytes(void) { return lz::kAttBlobBytes; }
 
 lz_status lz_attn_policy_pack(const lz_attn_policy* p, void* host_blob, int64_t cap) {
-  if (!p || !host_blob) return pfail(LZ_ERR_INVALID, "policy/blob is NULL");
-  if (cap < lz::kAttBlobBytes) return pfail(LZ_ERR_INVALID, "blob capacity too small");
-  if (p->obs_dim < 1 || p->obs_dim > lz::kPolMaxObs || p->act_dim < 1 || p->act_dim > lz::kPolMaxAct)
-    return pfail(LZ_ERR_UNSUPPORTED, "policy supports obs_dim 1..8 and act_dim 1..4");
-  const float* req[] = {p->fc1_w, p->fc1_b, p->in_proj_w, p->in_proj_b, p->out_proj_w,
-                        p->out_proj_b, p->post_w, p->post_b, p->pi_w1, p->pi_b1, p->pi_w2,
-                        p->pi_b2, p->vf_w1, p->vf_b1, p->vf_w2, p->vf_b2, p->act_w, p->act_b,
-                        p->val_w, p->val_b, p->log_std};
-  for (const float* q : req)
-    if (!q) return pfail(LZ_ERR_INVALID, "a policy weight pointer is NULL");
+  if (lz_status s = check_blob(p, host_blob, cap, lz::kAttBlobBytes)) return s;
+  if (lz_status s = check_dims(p->obs_dim, p->act_dim, lz::kPolMaxObs)) return s;
+  if (lz_status s = check_attn_ptrs(p)) return s;
   uint8_t* b = static_cast<uint8_t*>(host_blob);
   std::memset(b, 0, lz::kAttBlobBytes);
   pack_attn(b, p, nullptr, nullptr);
@@ -681,17 +693,10 @@ lz_status lz_attn_policy_pack(const lz_attn_policy* p, void* host_blob, int64_t 
 int64_t lz_attn_ln_policy_blob_bytes(void) { return lz::kLnBlobBytes; }
 
 lz_status lz_attn_ln_policy_pack(const lz_attn_ln_policy* q, void* host_blob, int64_t cap) {
-  if (!q || !host_blob) return pfail(LZ_ERR_INVALID, "policy/blob is NULL");
-  if (cap < lz::kLnBlobBytes) return pfail(LZ_ERR_INVALID, "blob capacity too small");
+  if (lz_status s = check_blob(q, host_blob, cap, lz::kLnBlobBytes)) return s;
   const lz_attn_policy* p = &q->attn;
-  if (p->obs_dim < 1 || p->obs_dim > lz::kLnMaxIn || p->act_dim < 1 || p->act_dim > lz::kPolMaxAct)
-    return pfail(LZ_ERR_UNSUPPORTED, "policy supports input dims 1..32 and act_dim 1..4");
-  const float* req[] = {p->fc1_w, p->fc1_b, p->in_proj_w, p->in_proj_b, p->out_proj_w,
-                        p->out_proj_b, p->post_w, p->post_b, p->pi_w1, p->pi_b1, p->pi_w2,
-                        p->pi_b2, p->vf_w1, p->vf_b1, p->vf_w2, p->vf_b2, p->act_w, p->act_b,
-                        p->val_w, p->val_b, p->log_std, q->ln_w, q->ln_b};
-  for (const float* r : req)
-    if (!r) return pfail(LZ_ERR_INVALID, "a policy weight pointer is NULL");
+  if (lz_status s = check_dims(p->obs_dim, p->act_dim, lz::kLnMaxIn)) return s;
+  if (lz_status s = check_attn_ptrs(p, q)) return s;
   uint8_t* b = static_cast<uint8_t*>(host_blob);
   std::memset(b, 0, lz::kLnBlobBytes);
   pack_attn(b, p, q->ln_w, q->ln_b);
@@ -703,27 +708,15 @@ int64_t lz_attn_policy_f32_blob_bytes(void) { return lz::kAFBlobBytes; }
 
 static lz_status pack_attn_f32_checked(const lz_attn_policy* p, const float* ln_w, const float* ln_b,
                                        void* host_blob, int64_t cap, int max_in) {
-  if (!p || !host_blob) return pfail(LZ_ERR_INVALID, "policy/blob is NULL");
-  if (cap < lz::kAFBlobBytes) return pfail(LZ_ERR_INVALID, "blob capacity too small");
-  if (p->obs_dim < 1 || p->obs_dim > max_in || p->act_dim < 1 || p->act_dim > lz::kPolMaxAct)
-    return pfail(LZ_ERR_UNSUPPORTED, max_in == lz::kPolMaxObs
-                                         ? "policy supports obs_dim 1..8 and act_dim 1..4"
-                                         : "policy supports input dims 1..32 and act_dim 1..4");
-  const float* req[] = {p->fc1_w, p->fc1_b, p->in_proj_w, p->in_proj_b, p->out_proj_w,
-                        p->out_proj_b, p->post_w, p->post_b, p->pi_w1, p->pi_b1, p->pi_w2,
-                        p->pi_b2, p->vf_w1, p->vf_b1, p->vf_w2, p->vf_b2, p->act_w, p->act_b,
-                        p->val_w, p->val_b, p->log_std};
-  for (const float* q : req)
-    if (!q) return pfail(LZ_ERR_INVALID, "a policy weight pointer is NULL");
+  if (lz_status s = check_blob(p, host_blob, cap, lz::kAFBlobBytes)) return s;
+  if (lz_status s = check_dims(p->obs_dim, p->act_dim, max_in)) return s;
+  if (lz_status s = check_attn_ptrs(p)) return s;
   uint8_t* b = static_cast<uint8_t*>(host_blob);
   std::memset(b, 0, lz::kAFBlobBytes);
   pack_attn_f32(b, p, ln_w, ln_b);
   pack_gauss(reinterpret_cast<float*>(b + lz::kAFLogStd), p->act_dim, p->log_std);
   lz::blob_tag(ln_w ? LZ_BLOB_ATTN_LN_F32 : LZ_BLOB_ATTN_F32, reinterpret_cast<uint32_t*>(b + lz::kAFTag));
-  float* tt = reinterpret_cast<float*>(b + lz::kAFTanh);
-  for (int k = 0; k < 72; ++k)
-    for (int j = 0; j < 8; ++j) tt[8 * k + j] = std::ldexp(kTanhTab[8 * k + j], -3 * j);
-  tt[8 * 72] = 1.0f;  // segment 72: the constant 1 (the rest stays zero)
+  write_tanh_table(reinterpret_cast<float*>(b + lz::kAFTanh));
   return LZ_OK;
 }
 
@@ -770,14 +763,12 @@ lz_status lz_attn_policy_pack_i8x4(const lz_attn_policy* p, void* host_blob, int
 }
 
 lz_status lz_attn_ln_policy_pack_i8x4(const lz_attn_ln_policy* p, void* host_blob, int64_t cap) {
-  if (!p) return pfail(LZ_ERR_INVALID, "policy is NULL");
-  if (!p->ln_w || !p->ln_b) return pfail(LZ_ERR_INVALID, "layer_norm weight / bias is NULL");
+  if (lz_status s = check_ln(p)) return s;
   return pack_attn_i8x4_checked(&p->attn, p->ln_w, p->ln_b, host_blob, cap, lz::kAFMaxIn);
 }
 
 lz_status lz_attn_ln_policy_pack_f32(const lz_attn_ln_policy* p, void* host_blob, int64_t cap) {
-  if (!p) return pfail(LZ_ERR_INVALID, "policy is NULL");
-  if (!p->ln_w || !p->ln_b) return pfail(LZ_ERR_INVALID, "layer_norm weight / bias is NULL");
+  if (lz_status s = check_ln(p)) return s;
   return pack_attn_f32_checked(&p->attn, p->ln_w, p->ln_b, host_blob, cap, lz::kAFMaxIn);
 }
 

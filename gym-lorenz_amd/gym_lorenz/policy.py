@@ -42,6 +42,7 @@ net_arch (same state_dict keys, same orthogonal init) -- the weight source when 
 absent and the fp32 reference in the tests.  An SB3 policy's ``state_dict()`` can be
 passed to ``set_params`` directly.
 """
+import contextlib
 import ctypes
 import math
 from dataclasses import dataclass
@@ -198,16 +199,24 @@ def reference_forward_bf16(state_dict, obs):
     layer's input activations rounded to bf16, round-to-nearest-even), fp32 bias and
     accumulation, tanh(acc / s).  Differs from the kernel only in fp32 summation order
     and the tanh implementation (|err| <= 2e-7).  Returns (mean, value)."""
-    sd = {k: torch.as_tensor(np.asarray(_np(v)), dtype=torch.float32) for k, v in state_dict.items()}
-    x = _bf(torch.as_tensor(obs, dtype=torch.float32))
+    return _bf16_tanh_nets(state_dict, _bf(torch.as_tensor(obs, dtype=torch.float32)))
+
+
+def _t(sd, k):
+    return torch.as_tensor(np.asarray(_np(sd[k])), dtype=torch.float32)
+
+
+def _bf16_tanh_nets(sd, feat):
+    """The restated forwards' tail: the two [128, 128] Tanh nets and their heads on the
+    bf16-valued features (the MlpPolicy: observations) -> (mean, value)."""
     s = torch.tensor(TANH_SCALE)
 
     def net(prefix, w3, b3):
-        h = x
+        h = feat
         for layer in (".0", ".2"):
-            acc = h @ _bf(s * sd[prefix + layer + ".weight"]).T + s * sd[prefix + layer + ".bias"]
+            acc = h @ _bf(s * _t(sd, prefix + layer + ".weight")).T + s * _t(sd, prefix + layer + ".bias")
             h = _bf(torch.tanh(acc / s))
-        return h @ _bf(sd[w3]).T + sd[b3]
+        return h @ _bf(_t(sd, w3)).T + _t(sd, b3)
 
     mean = net("mlp_extractor.policy_net", "action_net.weight", "action_net.bias")
     value = net("mlp_extractor.value_net", "value_net.weight", "value_net.bias").flatten()
@@ -259,24 +268,16 @@ def attn_folded_post(sd):
     return wf, bf
 
 
-def reference_forward_attn_bf16(state_dict, obs):
-    """lz_rollout_policy_attn's arithmetic restated in torch: bf16 obs / weights /
-    tokens / head outputs / features (RNE), fp32 accumulation and attention, the Q
-    projection pre-scaled by ATTN_Q_SCALE and a base-2 softmax, out_proj folded into
-    post_attention_fc in float64, the Tanh nets as reference_forward_bf16.  Differs
-    from the kernel in fp32 summation order and the exp2 / rcp / tanh implementations.
-    Returns (mean, value)."""
-    sd = state_dict
+def _bf16_attn_stem(sd, obs):
+    """The bf16 attention forwards up to the head outputs: bf16 obs / weights / tokens
+    (RNE), fp32 accumulation and attention, the Q projection pre-scaled by ATTN_Q_SCALE
+    and a base-2 softmax.  Returns the bf16-valued tokens and head outputs, [n, 8, 16]."""
     f32 = torch.float32
-
-    def t(k):
-        return torch.as_tensor(np.asarray(_np(sd[k])), dtype=f32)
-
     x = _bf(torch.as_tensor(obs, dtype=f32))
     n = x.shape[0]
-    tok = _bf(torch.relu(x @ _bf(t(_fe_key(sd, "fc1.weight"))).T + t(_fe_key(sd, "fc1.bias"))))
+    tok = _bf(torch.relu(x @ _bf(_t(sd, _fe_key(sd, "fc1.weight"))).T + _t(sd, _fe_key(sd, "fc1.bias"))))
     tok = tok.view(n, 8, 16)
-    w_in, b_in = t(_fe_key(sd, ATTN_FE_KEYS[2])), t(_fe_key(sd, ATTN_FE_KEYS[3]))
+    w_in, b_in = _t(sd, _fe_key(sd, ATTN_FE_KEYS[2])), _t(sd, _fe_key(sd, ATTN_FE_KEYS[3]))
     c = torch.tensor(np.float64(ATTN_Q_SCALE))
     wq = _bf((c.double() * w_in[:16].double()).to(f32))
     bq = (c.double() * b_in[:16].double()).to(f32)
@@ -287,22 +288,20 @@ def reference_forward_attn_bf16(state_dict, obs):
     s = q @ k.transpose(-1, -2)
     p = torch.exp2(s - s.amax(-1, keepdim=True))
     o = (p @ v) * (1.0 / p.sum(-1, keepdim=True))  # normalised after the weighted sum
-    a = _bf(o.transpose(1, 2).reshape(n, 8, 16))
-    wf, bfold = attn_folded_post(sd)
-    feat = bfold.to(f32) + torch.einsum("nid,ifd->nf", a, _bf(wf.to(f32)))
-    feat = _bf(torch.relu(feat))
-    s_t = torch.tensor(TANH_SCALE)
+    return tok, _bf(o.transpose(1, 2).reshape(n, 8, 16))
 
-    def net(prefix, w3, b3):
-        h = feat
-        for layer in (".0", ".2"):
-            acc = h @ _bf(s_t * t(prefix + layer + ".weight")).T + s_t * t(prefix + layer + ".bias")
-            h = _bf(torch.tanh(acc / s_t))
-        return h @ _bf(t(w3)).T + t(b3)
 
-    mean = net("mlp_extractor.policy_net", "action_net.weight", "action_net.bias")
-    value = net("mlp_extractor.value_net", "value_net.weight", "value_net.bias").flatten()
-    return mean, value
+def reference_forward_attn_bf16(state_dict, obs):
+    """lz_rollout_policy_attn's arithmetic restated in torch: bf16 obs / weights /
+    tokens / head outputs / features (RNE), fp32 accumulation and attention, the Q
+    projection pre-scaled by ATTN_Q_SCALE and a base-2 softmax, out_proj folded into
+    post_attention_fc in float64, the Tanh nets as reference_forward_bf16.  Differs
+    from the kernel in fp32 summation order and the exp2 / rcp / tanh implementations.
+    Returns (mean, value)."""
+    _, a = _bf16_attn_stem(state_dict, obs)
+    wf, bfold = attn_folded_post(state_dict)
+    feat = bfold.to(torch.float32) + torch.einsum("nid,ifd->nf", a, _bf(wf.to(torch.float32)))
+    return _bf16_tanh_nets(state_dict, _bf(torch.relu(feat)))
 
 
 def reference_forward_attn_ln_bf16(state_dict, obs):
@@ -313,48 +312,19 @@ def reference_forward_attn_ln_bf16(state_dict, obs):
     operands) + ReLU, the Tanh nets.  obs: the (stacked) policy input.  Returns
     (mean, value)."""
     sd = state_dict
-    f32 = torch.float32
 
-    def t(k):
-        return torch.as_tensor(np.asarray(_np(sd[k])), dtype=f32)
+    def t(name):
+        return _t(sd, _fe_key(sd, name))
 
-    x = _bf(torch.as_tensor(obs, dtype=f32))
-    n = x.shape[0]
-    tok = _bf(torch.relu(x @ _bf(t(_fe_key(sd, "fc1.weight"))).T + t(_fe_key(sd, "fc1.bias"))))
-    tok = tok.view(n, 8, 16)
-    w_in, b_in = t(_fe_key(sd, ATTN_FE_KEYS[2])), t(_fe_key(sd, ATTN_FE_KEYS[3]))
-    c = torch.tensor(np.float64(ATTN_Q_SCALE))
-    wq = _bf((c.double() * w_in[:16].double()).to(f32))
-    bq = (c.double() * b_in[:16].double()).to(f32)
-    q = tok @ wq.T + bq
-    k = tok @ _bf(w_in[16:32]).T + b_in[16:32]
-    v = tok @ _bf(w_in[32:48]).T + b_in[32:48]
-    q, k, v = (z.view(n, 8, 4, 4).transpose(1, 2) for z in (q, k, v))
-    s = q @ k.transpose(-1, -2)
-    p = torch.exp2(s - s.amax(-1, keepdim=True))
-    o = (p @ v) * (1.0 / p.sum(-1, keepdim=True))
-    a = _bf(o.transpose(1, 2).reshape(n, 8, 16))
-    y = a @ _bf(t(_fe_key(sd, ATTN_FE_KEYS[4]))).T + t(_fe_key(sd, ATTN_FE_KEYS[5]))
+    tok, a = _bf16_attn_stem(sd, obs)
+    y = a @ _bf(t(ATTN_FE_KEYS[4])).T + t(ATTN_FE_KEYS[5])
     z = y + tok
     mu = z.mean(-1, keepdim=True)
     z = z - mu
     var = (z * z).mean(-1, keepdim=True)
-    u = _bf(z * torch.rsqrt(var + 1e-5) * t(_fe_key(sd, "layer_norm.weight"))
-            + t(_fe_key(sd, "layer_norm.bias")))
-    feat = _bf(torch.relu(u.reshape(n, 128) @ _bf(t(_fe_key(sd, ATTN_FE_KEYS[6]))).T
-                          + t(_fe_key(sd, ATTN_FE_KEYS[7]))))
-    s_t = torch.tensor(TANH_SCALE)
-
-    def net(prefix, w3, b3):
-        h = feat
-        for layer in (".0", ".2"):
-            acc = h @ _bf(s_t * t(prefix + layer + ".weight")).T + s_t * t(prefix + layer + ".bias")
-            h = _bf(torch.tanh(acc / s_t))
-        return h @ _bf(t(w3)).T + t(b3)
-
-    mean = net("mlp_extractor.policy_net", "action_net.weight", "action_net.bias")
-    value = net("mlp_extractor.value_net", "value_net.weight", "value_net.bias").flatten()
-    return mean, value
+    u = _bf(z * torch.rsqrt(var + 1e-5) * t("layer_norm.weight") + t("layer_norm.bias"))
+    feat = _bf(torch.relu(u.reshape(-1, 128) @ _bf(t(ATTN_FE_KEYS[6])).T + t(ATTN_FE_KEYS[7])))
+    return _bf16_tanh_nets(sd, feat)
 
 
 def _np(v):
@@ -381,33 +351,6 @@ def _mlp_policy_struct(state_dict, obs_dim, act_dim):
     for f, a in zip(_FIELDS, arrs):
         setattr(p, f, a.ctypes.data)
     return p, H, arrs  # arrs keep the weights alive while p points at them
-
-
-def pack_policy_f32(state_dict, obs_dim, act_dim):
-    """lz_policy_pack_f32: SB3 state_dict (net_arch pi=[H,H] vf=[H,H], H <= 128) ->
-    uint8 numpy blob of the float32 kernel (host; needs no GPU)."""
-    p, H, _keep = _mlp_policy_struct(state_dict, obs_dim, act_dim)
-    blob = np.zeros(int(nat.lib.lz_policy_f32_blob_bytes()), np.uint8)
-    nat.check(nat.lib.lz_policy_pack_f32(ctypes.byref(p), H, blob.ctypes.data, blob.size))
-    return blob
-
-
-def pack_policy_i8x4(state_dict, obs_dim, act_dim):
-    """lz_policy_pack_i8x4: the float32 MlpPolicy blob with each net's layer 2 as exact
-    4-digit int8 fixed-point products (precision="i8x4"; oracle orc_mlp_i8x4)."""
-    p, H, _keep = _mlp_policy_struct(state_dict, obs_dim, act_dim)
-    blob = np.zeros(int(nat.lib.lz_policy_f32_blob_bytes()), np.uint8)
-    nat.check(nat.lib.lz_policy_pack_i8x4(ctypes.byref(p), H, blob.ctypes.data, blob.size))
-    return blob
-
-
-def pack_policy(state_dict, obs_dim, act_dim):
-    """lz_policy_pack / lz_policy_pack_hidden: SB3 state_dict (net_arch pi=[H,H]
-    vf=[H,H], H <= 128) -> uint8 numpy blob of the bf16 kernel (host; needs no GPU)."""
-    p, H, _keep = _mlp_policy_struct(state_dict, obs_dim, act_dim)
-    blob = np.zeros(int(nat.lib.lz_policy_blob_bytes()), np.uint8)
-    nat.check(nat.lib.lz_policy_pack_hidden(ctypes.byref(p), H, blob.ctypes.data, blob.size))
-    return blob
 
 
 def _attn_struct(state_dict, in_dim, act_dim, features_dim, ln):
@@ -439,95 +382,92 @@ def _attn_struct(state_dict, in_dim, act_dim, features_dim, ln):
     return q, arrs
 
 
+# The packers, one row per (family, precision): the C pack function, the function that
+# gives its blob's size, and the LZ_BLOB_* tag the blob carries (None: the bf16 blobs carry
+# none).  A new policy family or precision is added here and in _LAUNCH.
+_PACKERS = {
+    ("mlp", "bf16"): ("lz_policy_pack_hidden", "lz_policy_blob_bytes", None),
+    ("mlp", "fp32"): ("lz_policy_pack_f32", "lz_policy_f32_blob_bytes", nat.BLOB_MLP_F32),
+    ("mlp", "i8x4"): ("lz_policy_pack_i8x4", "lz_policy_f32_blob_bytes", nat.BLOB_MLP_I8X4),
+    ("attn", "bf16"): ("lz_attn_policy_pack", "lz_attn_policy_blob_bytes", None),
+    ("attn", "fp32"): ("lz_attn_policy_pack_f32", "lz_attn_policy_f32_blob_bytes", nat.BLOB_ATTN_F32),
+    ("attn", "i8x4"): ("lz_attn_policy_pack_i8x4", "lz_attn_policy_f32_blob_bytes", nat.BLOB_ATTN_I8X4),
+    ("attn_ln", "bf16"): ("lz_attn_ln_policy_pack", "lz_attn_ln_policy_blob_bytes", None),
+    ("attn_ln", "fp32"): ("lz_attn_ln_policy_pack_f32", "lz_attn_policy_f32_blob_bytes",
+                          nat.BLOB_ATTN_LN_F32),
+    ("attn_ln", "i8x4"): ("lz_attn_ln_policy_pack_i8x4", "lz_attn_policy_f32_blob_bytes",
+                          nat.BLOB_ATTN_LN_I8X4),
+}
+
+
+def _pack(family, precision, state_dict, in_dim, act_dim, features_dim=64):
+    """SB3 state_dict -> the uint8 numpy blob of _PACKERS[family, precision] (host; needs
+    no GPU).  in_dim: the policy's input width (the stacked one for "attn_ln")."""
+    pack, blob_bytes, _tag = _PACKERS[family, precision]
+    if family == "mlp":
+        p, H, _keep = _mlp_policy_struct(state_dict, in_dim, act_dim)
+        args = (ctypes.byref(p), H)
+    else:
+        p, _keep = _attn_struct(state_dict, in_dim, act_dim, features_dim, family == "attn_ln")
+        args = (ctypes.byref(p),)
+    blob = np.zeros(int(getattr(nat.lib, blob_bytes)()), np.uint8)
+    nat.check(getattr(nat.lib, pack)(*args, blob.ctypes.data, blob.size))
+    return blob
+
+
+def pack_policy(state_dict, obs_dim, act_dim):
+    """lz_policy_pack / lz_policy_pack_hidden: SB3 state_dict (net_arch pi=[H,H]
+    vf=[H,H], H <= 128) -> uint8 numpy blob of the bf16 kernel (host; needs no GPU)."""
+    return _pack("mlp", "bf16", state_dict, obs_dim, act_dim)
+
+
+def pack_policy_f32(state_dict, obs_dim, act_dim):
+    """lz_policy_pack_f32: SB3 state_dict (net_arch pi=[H,H] vf=[H,H], H <= 128) ->
+    uint8 numpy blob of the float32 kernel (host; needs no GPU)."""
+    return _pack("mlp", "fp32", state_dict, obs_dim, act_dim)
+
+
+def pack_policy_i8x4(state_dict, obs_dim, act_dim):
+    """lz_policy_pack_i8x4: the float32 MlpPolicy blob with each net's layer 2 as exact
+    4-digit int8 fixed-point products (precision="i8x4"; oracle orc_mlp_i8x4)."""
+    return _pack("mlp", "i8x4", state_dict, obs_dim, act_dim)
+
+
 def pack_attn_policy_f32(state_dict, obs_dim, act_dim, features_dim=64):
     """lz_attn_policy_pack_f32: code/train.py's attention actor-critic at SB3's float32
     precision (lz_rollout_policy_attn_f32) -> uint8 numpy blob (host; needs no GPU)."""
-    p, _keep = _attn_struct(state_dict, obs_dim, act_dim, features_dim, False)
-    blob = np.zeros(int(nat.lib.lz_attn_policy_f32_blob_bytes()), np.uint8)
-    nat.check(nat.lib.lz_attn_policy_pack_f32(ctypes.byref(p), blob.ctypes.data, blob.size))
-    return blob
+    return _pack("attn", "fp32", state_dict, obs_dim, act_dim, features_dim)
 
 
 def pack_attn_ln_policy_f32(state_dict, in_dim, act_dim, features_dim=64):
     """lz_attn_ln_policy_pack_f32: code/lorenz_filter/train.py's residual + LayerNorm
     policy at float32 precision (in_dim = the stacked observation width)."""
-    p, _keep = _attn_struct(state_dict, in_dim, act_dim, features_dim, True)
-    blob = np.zeros(int(nat.lib.lz_attn_policy_f32_blob_bytes()), np.uint8)
-    nat.check(nat.lib.lz_attn_ln_policy_pack_f32(ctypes.byref(p), blob.ctypes.data, blob.size))
-    return blob
+    return _pack("attn_ln", "fp32", state_dict, in_dim, act_dim, features_dim)
 
 
 def pack_attn_policy_i8x4(state_dict, obs_dim, act_dim, features_dim=64):
     """lz_attn_policy_pack_i8x4: code/train.py's attention actor-critic with the nets' two
     wide layers as exact 4-digit int8 fixed-point products (precision="i8x4"; the float32
     blob's size and layout otherwise) -> uint8 numpy blob (host; needs no GPU)."""
-    p, _keep = _attn_struct(state_dict, obs_dim, act_dim, features_dim, False)
-    blob = np.zeros(int(nat.lib.lz_attn_policy_f32_blob_bytes()), np.uint8)
-    nat.check(nat.lib.lz_attn_policy_pack_i8x4(ctypes.byref(p), blob.ctypes.data, blob.size))
-    return blob
+    return _pack("attn", "i8x4", state_dict, obs_dim, act_dim, features_dim)
 
 
 def pack_attn_ln_policy_i8x4(state_dict, in_dim, act_dim, features_dim=64):
     """lz_attn_ln_policy_pack_i8x4: code/lorenz_filter/train.py's residual + LayerNorm
     policy, precision="i8x4" (in_dim = the stacked observation width)."""
-    p, _keep = _attn_struct(state_dict, in_dim, act_dim, features_dim, True)
-    blob = np.zeros(int(nat.lib.lz_attn_policy_f32_blob_bytes()), np.uint8)
-    nat.check(nat.lib.lz_attn_ln_policy_pack_i8x4(ctypes.byref(p), blob.ctypes.data, blob.size))
-    return blob
+    return _pack("attn_ln", "i8x4", state_dict, in_dim, act_dim, features_dim)
 
 
 def pack_attn_policy(state_dict, obs_dim, act_dim, features_dim=64):
     """lz_attn_policy_pack: SB3 state_dict of code/train.py's attention actor-critic ->
     uint8 numpy blob (host; needs no GPU)."""
-    if features_dim != 64:
-        raise ValueError("the fused kernel implements features_dim=64 (code/train.py:100)")
-    keys = [_fe_key(state_dict, k) for k in ATTN_FE_KEYS] + list(KEYS)
-    for key in KEYS:
-        if key not in state_dict:
-            raise KeyError("policy state_dict lacks %r" % key)
-    arrs = [np.ascontiguousarray(_np(state_dict[k]), dtype=np.float32) for k in keys]
-    F = features_dim
-    shapes = [(HIDDEN, obs_dim), (HIDDEN,), (48, 16), (48,), (16, 16), (16,), (F, HIDDEN), (F,)] + [
-        (HIDDEN, F), (HIDDEN,), (HIDDEN, HIDDEN), (HIDDEN,)] * 2 + [
-        (act_dim, HIDDEN), (act_dim,), (1, HIDDEN), (1,), (act_dim,)]
-    for key, a, shp in zip(keys, arrs, shapes):
-        if a.shape != shp:
-            raise ValueError("%s has shape %s, expected %s" % (key, a.shape, shp))
-    p = nat.LzAttnPolicy()
-    p.obs_dim, p.act_dim = int(obs_dim), int(act_dim)
-    for f, a in zip(_ATTN_FE_FIELDS + _FIELDS, arrs):
-        setattr(p, f, a.ctypes.data)
-    blob = np.zeros(int(nat.lib.lz_attn_policy_blob_bytes()), np.uint8)
-    nat.check(nat.lib.lz_attn_policy_pack(ctypes.byref(p), blob.ctypes.data, blob.size))
-    return blob
+    return _pack("attn", "bf16", state_dict, obs_dim, act_dim, features_dim)
 
 
 def pack_attn_ln_policy(state_dict, in_dim, act_dim, features_dim=64):
     """lz_attn_ln_policy_pack: code/lorenz_filter/train.py's policy (in_dim = the
     stacked observation width) -> uint8 numpy blob (host; needs no GPU)."""
-    if features_dim != 64:
-        raise ValueError("the fused kernel implements features_dim=64")
-    keys = [_fe_key(state_dict, k) for k in ATTN_FE_KEYS] + list(KEYS) + [
-        _fe_key(state_dict, "layer_norm.weight"), _fe_key(state_dict, "layer_norm.bias")]
-    for key in KEYS:
-        if key not in state_dict:
-            raise KeyError("policy state_dict lacks %r" % key)
-    arrs = [np.ascontiguousarray(_np(state_dict[k]), dtype=np.float32) for k in keys]
-    F = features_dim
-    shapes = [(HIDDEN, in_dim), (HIDDEN,), (48, 16), (48,), (16, 16), (16,), (F, HIDDEN), (F,)] + [
-        (HIDDEN, F), (HIDDEN,), (HIDDEN, HIDDEN), (HIDDEN,)] * 2 + [
-        (act_dim, HIDDEN), (act_dim,), (1, HIDDEN), (1,), (act_dim,), (16,), (16,)]
-    for key, a, shp in zip(keys, arrs, shapes):
-        if a.shape != shp:
-            raise ValueError("%s has shape %s, expected %s" % (key, a.shape, shp))
-    p = nat.LzAttnLnPolicy()
-    p.attn.obs_dim, p.attn.act_dim = int(in_dim), int(act_dim)
-    for f, a in zip(_ATTN_FE_FIELDS + _FIELDS, arrs):
-        setattr(p.attn, f, a.ctypes.data)
-    p.ln_w, p.ln_b = arrs[-2].ctypes.data, arrs[-1].ctypes.data
-    blob = np.zeros(int(nat.lib.lz_attn_ln_policy_blob_bytes()), np.uint8)
-    nat.check(nat.lib.lz_attn_ln_policy_pack(ctypes.byref(p), blob.ctypes.data, blob.size))
-    return blob
+    return _pack("attn_ln", "bf16", state_dict, in_dim, act_dim, features_dim)
 
 
 @dataclass
@@ -557,14 +497,125 @@ def _p(t):
 
 def blob_format(attention, attention_ln, i8x4):
     """The LZ_BLOB_* format a float32 / i8x4 launch reads (entry point + LZ_POLICY_I8X4)."""
-    if attention_ln:
-        return nat.BLOB_ATTN_LN_I8X4 if i8x4 else nat.BLOB_ATTN_LN_F32
-    if attention:
-        return nat.BLOB_ATTN_I8X4 if i8x4 else nat.BLOB_ATTN_F32
-    return nat.BLOB_MLP_I8X4 if i8x4 else nat.BLOB_MLP_F32
+    family = "attn_ln" if attention_ln else "attn" if attention else "mlp"
+    return _PACKERS[family, "i8x4" if i8x4 else "fp32"][2]
 
 
-class FusedRolloutCollector:
+# The entry points, one row per (kind, family, precision), laid out like kPolicyTable in
+# lz_api.cpp; precision "i8x4" runs the "fp32" row with LZ_POLICY_I8X4.  The "attn_ln" rows
+# take (n_stack, stack_in, stack_out) after the arguments, the "trace" rows an lz_eval_trace
+# last.  "step" is the per-step VecNormalize collect's launch (lz_rollout_policy_f32_vn is
+# the library's own loop over it).
+_LAUNCH = {
+    ("rollout", "mlp", "bf16"): "lz_rollout_policy",
+    ("rollout", "attn", "bf16"): "lz_rollout_policy_attn",
+    ("rollout", "attn_ln", "bf16"): "lz_rollout_policy_attn_stack",
+    ("rollout", "mlp", "fp32"): "lz_rollout_policy_f32",
+    ("rollout", "attn", "fp32"): "lz_rollout_policy_attn_f32",
+    ("rollout", "attn_ln", "fp32"): "lz_rollout_policy_attn_stack_f32",
+    ("step", "mlp", "fp32"): "lz_policy_step_f32",
+    ("evaluate", "mlp", "fp32"): "lz_evaluate_policy_f32",
+    ("evaluate", "attn", "fp32"): "lz_evaluate_policy_attn_f32",
+    ("evaluate", "attn_ln", "fp32"): "lz_evaluate_policy_attn_stack_f32",
+    ("trace", "mlp", "fp32"): "lz_evaluate_policy_f32_trace",
+    ("trace", "attn", "fp32"): "lz_evaluate_policy_attn_f32_trace",
+    ("trace", "attn_ln", "fp32"): "lz_evaluate_policy_attn_stack_f32_trace",
+}
+
+
+class _PolicySeam:
+    """What FusedRolloutCollector and FusedEvaluator share between a state_dict and a
+    launch: the policy family and the frame-stack rules, the packed and tag-checked blob,
+    the carried observations / frame stack, and the call into _LAUNCH's entry point on the
+    env handle's stream.  A subclass sets env, device, n, O, A, obs_rms and _what."""
+
+    _what = "rollout"          # the noun of the refusals
+    attention = attention_ln = False
+    f32, i8x4 = True, False    # the evaluator's stance; the collector sets its own
+    blob = last_obs = last_stack = None
+
+    @property
+    def family(self):
+        return "attn_ln" if self.attention_ln else "attn" if self.attention else "mlp"
+
+    def _init_frame_stack(self, frame_stack):
+        # SB3 VecFrameStack(n_stack) between the env and the policy
+        # (code/lorenz_filter/train.py:115): the stack is carried on the device
+        self.frame_stack = int(frame_stack)
+        if self.frame_stack not in (1, 4):
+            raise ValueError("frame_stack must be 1 or 4 (the fused kernel's instantiations)")
+        if self.frame_stack > 1 and self.obs_rms is not None:
+            raise ValueError("the frame-stacked %s stacks raw observations (no VecNormalize)" % self._what)
+
+    def _select(self, state_dict):
+        """The family of the state_dict's keys (as FusedRolloutCollector.set_params says)."""
+        self.attention = is_attention_policy(state_dict)
+        self.attention_ln = is_attention_ln_policy(state_dict)
+        if self.frame_stack > 1 and not self.attention_ln:
+            raise ValueError("frame_stack > 1 runs code/lorenz_filter/train.py's policy "
+                             "(the residual + LayerNorm attention extractor)")
+
+    def _pack_params(self, state_dict, precision):
+        if self.attention_ln and self.obs_rms is not None:
+            raise ValueError("the LayerNorm attention %s takes raw observations" % self._what)
+        in_dim = self.frame_stack * self.O if self.attention_ln else self.O
+        return _pack(self.family, precision, state_dict, in_dim, self.A)
+
+    def _set_blob(self, blob):
+        """Upload a packed blob; a float32 / i8x4 one only if its format tag is the one the
+        launch this object makes will expect."""
+        if self.f32:
+            want = blob_format(self.attention, self.attention_ln, self.i8x4)
+            got = int(nat.lib.lz_policy_blob_format(blob.ctypes.data, blob.size))
+            if got != want:
+                raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "policy blob format %d, the launch "
+                                         "expects %d" % (got, want))
+        self.blob = torch.from_numpy(blob).to(self.device)
+
+    def _start_from(self, obs):
+        """The next launch starts from obs and a fresh frame stack (StackedObservations.reset:
+        zeros, the first frame last)."""
+        self.last_obs = obs.clone()
+        self.last_stack = torch.zeros((self.n, self.frame_stack * self.O), dtype=torch.float32,
+                                      device=self.device)
+        self.last_stack[:, -self.O:] = obs
+        return self.last_obs
+
+    @contextlib.contextmanager
+    def _on_env_stream(self):
+        """The launches run on the env handle's stream: the caller's current stream (where
+        the buffers were allocated and blob / last_obs written, and where the results are
+        read) is ordered around them both ways.  Yields the caller's stream."""
+        caller = torch.cuda.current_stream(self.device)
+        es = self.env.stream
+        if es != caller:
+            es.wait_stream(caller)
+        yield caller
+        if es != caller:
+            caller.wait_stream(es)
+
+    def _launch(self, kind, args, trace=None):
+        """Call _LAUNCH's entry point for this policy; returns the frame stack it wrote
+        (None unless the family carries one)."""
+        fn = getattr(nat.lib, _LAUNCH[kind, self.family, "fp32" if self.f32 else "bf16"])
+        stack_out, extra = None, ()
+        if self.attention_ln:
+            stack_out = torch.empty((self.n, self.frame_stack * self.O), dtype=torch.float32,
+                                    device=self.device)
+            extra = (self.frame_stack, _p(self.last_stack), _p(stack_out))
+        if trace is not None:
+            extra += (ctypes.byref(trace),)
+        nat.check(fn(self.env._h, ctypes.byref(args), *extra))
+        return stack_out
+
+    def _hand_over(self, obs_last, stack_out):
+        self._keep = (self.blob, self.last_obs, self.last_stack)  # alive until consumed
+        self.last_obs = obs_last
+        if stack_out is not None:
+            self.last_stack = stack_out
+
+
+class FusedRolloutCollector(_PolicySeam):
     """OnPolicyAlgorithm.collect_rollouts over a BatchedEnv, one launch per rollout.
 
     backend:       gym_lorenz.core.BatchedEnv (float32, autoreset)
@@ -613,20 +664,8 @@ class FusedRolloutCollector:
         if vecnorm_update not in (None, "step", "rollout"):
             raise ValueError("vecnorm_update must be 'step' or 'rollout'")
         self.vecnorm_update = vecnorm_update
-        self.f32 = False
-        self.i8x4 = False
-        self.blob = None
-        self.attention = False
-        self.attention_ln = False
-        # SB3 VecFrameStack(n_stack) between the env and the policy
-        # (code/lorenz_filter/train.py:115): the stack is carried on the device
-        self.frame_stack = int(frame_stack)
-        if self.frame_stack not in (1, 4):
-            raise ValueError("frame_stack must be 1 or 4 (the fused kernel's instantiations)")
-        if self.frame_stack > 1 and obs_rms is not None:
-            raise ValueError("the frame-stacked rollout stacks raw observations (no VecNormalize)")
-        self.last_stack = None
-        self.last_obs = None
+        self.f32 = False  # until set_params
+        self._init_frame_stack(frame_stack)
         self.last_episode_starts = torch.ones((self.n,), dtype=torch.float32, device=self.device)
         if state_dict is not None:
             self.set_params(state_dict)
@@ -635,40 +674,19 @@ class FusedRolloutCollector:
         """Pack and upload the actor-critic weights (call after every optimizer step).
         A state_dict with code/train.py's AttentionFeaturesExtractor selects the
         attention kernel (lz_rollout_policy_attn), any other the MlpPolicy kernel."""
-        self.attention = is_attention_policy(state_dict)
-        self.attention_ln = is_attention_ln_policy(state_dict)
-        if self.frame_stack > 1 and not self.attention_ln:
-            raise ValueError("frame_stack > 1 runs code/lorenz_filter/train.py's policy "
-                             "(the residual + LayerNorm attention extractor)")
+        self._select(state_dict)
         self.f32 = self.precision != "bf16"
         self.i8x4 = self.precision == "i8x4"
-        if self.i8x4 and not (self.attention or self.attention_ln):
+        if self.i8x4 and self.family == "mlp":
             if self.env.system_name not in ("lorenz3", "lorenz4", "pmsm", "hr"):
                 raise ValueError("the i8x4 MlpPolicy runs LORENZ3 / LORENZ4 / PMSM / HR")
             if self.obs_rms is not None and self.training and self.vecnorm_update != "rollout":
                 raise ValueError("precision='i8x4' with a training VecNormalize needs "
                                  "vecnorm_update='rollout' (the per-step collect is float32)")
-        if self.attention_ln:
-            if self.obs_rms is not None:
-                raise ValueError("the LayerNorm attention rollout takes raw observations")
-            blob = (pack_attn_ln_policy_i8x4 if self.i8x4 else
-                    pack_attn_ln_policy_f32 if self.f32 else pack_attn_ln_policy)(
-                state_dict, self.frame_stack * self.O, self.A)
-        elif self.attention:
-            blob = (pack_attn_policy_i8x4 if self.i8x4 else
-                    pack_attn_policy_f32 if self.f32 else pack_attn_policy)(state_dict, self.O, self.A)
-        else:
-            blob = (pack_policy_i8x4 if self.i8x4 else
-                    pack_policy_f32 if self.f32 else pack_policy)(state_dict, self.O, self.A)
-        if self.vecnorm_update == "step" and (not self.f32 or self.attention or self.attention_ln):
+        blob = self._pack_params(state_dict, self.precision or "fp32")
+        if self.vecnorm_update == "step" and (not self.f32 or self.family != "mlp"):
             raise ValueError("vecnorm_update='step' runs the float32 MlpPolicy kernel")
-        if self.f32:  # the packer's format tag against the launch this collector will make
-            want = blob_format(self.attention, self.attention_ln, self.i8x4)
-            got = int(nat.lib.lz_policy_blob_format(blob.ctypes.data, blob.size))
-            if got != want:
-                raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "policy blob format %d, the launch "
-                                         "expects %d" % (got, want))
-        self.blob = torch.from_numpy(blob).to(self.device)
+        self._set_blob(blob)
 
     @property
     def per_step_vecnorm(self):
@@ -690,12 +708,7 @@ class FusedRolloutCollector:
 
     def reset(self):
         """VecEnv.reset(): fresh episodes; the next rollout starts from their obs."""
-        obs = self.env.reset()
-        self.last_obs = obs.clone()
-        # StackedObservations.reset: zeros, the first frame last
-        self.last_stack = torch.zeros((self.n, self.frame_stack * self.O), dtype=torch.float32,
-                                      device=self.device)
-        self.last_stack[:, -self.O:] = obs
+        self._start_from(self.env.reset())
         self.last_episode_starts.fill_(1.0)
         if self.obs_rms is not None and self.training:
             if self.per_step_vecnorm:
@@ -742,31 +755,21 @@ class FusedRolloutCollector:
         r.obs_moments = _p(mom)
         r.done_idx, r.terminal_obs, r.cap, r.n_done = _p(didx), _p(tobs), self.capture_terminal, _p(ndone)
         stack_out = None
-        # the rollout runs on the env handle's stream; the caller's current stream (where
-        # the buffers above were allocated and blob / last_obs written, and where the
-        # follow-up kernels below run) is ordered around it both ways
-        caller = torch.cuda.current_stream(dev)
-        es = self.env.stream
-        if es != caller:
-            es.wait_stream(caller)
-        if self.attention_ln:
-            stack_out = torch.empty((n, SO), dtype=f32, device=dev)
-            launch = (nat.lib.lz_rollout_policy_attn_stack_f32 if self.f32
-                      else nat.lib.lz_rollout_policy_attn_stack)
-            nat.check(launch(self.env._h, ctypes.byref(r), self.frame_stack, _p(self.last_stack),
-                             _p(stack_out)))
-        elif per_step:
-            state = ctypes.c_void_p(self.obs_rms.state.data_ptr())
-            if self.group is None:
+        with self._on_env_stream() as caller:
+            state = ctypes.c_void_p(self.obs_rms.state.data_ptr()) if per_step else None
+            if not per_step:
+                stack_out = self._launch("rollout", r)
+            elif self.group is None:
                 nat.check(nat.lib.lz_rollout_policy_f32_vn(self.env._h, ctypes.byref(r), state))
             else:  # every step's batch moments all-reduced before its update
+                step = getattr(nat.lib, _LAUNCH["step", "mlp", "fp32"])
+                es = self.env.stream
                 mom = torch.empty((1 + 2 * O,), dtype=torch.float64, device=dev)
                 rh = self.obs_rms._h
                 nat.check(nat.lib.lz_rms_set_stream(rh, ctypes.c_void_p(caller.cuda_stream)))
                 for k in range(K + 1):
-                    nat.check(nat.lib.lz_policy_step_f32(self.env._h, ctypes.byref(r), k, state,
-                                                         ctypes.c_void_p(mom.data_ptr()) if k < K
-                                                         else None))
+                    nat.check(step(self.env._h, ctypes.byref(r), k, state,
+                                   ctypes.c_void_p(mom.data_ptr()) if k < K else None))
                     if k < K:
                         if es != caller:
                             caller.wait_stream(es)
@@ -774,23 +777,13 @@ class FusedRolloutCollector:
                         nat.check(nat.lib.lz_rms_update(rh, ctypes.c_void_p(mom.data_ptr())))
                         if es != caller:
                             es.wait_stream(caller)
-        else:
-            launch = ((nat.lib.lz_rollout_policy_attn_f32 if self.f32 else nat.lib.lz_rollout_policy_attn)
-                      if self.attention else
-                      nat.lib.lz_rollout_policy_f32 if self.f32 else nat.lib.lz_rollout_policy)
-            nat.check(launch(self.env._h, ctypes.byref(r)))
-        if es != caller:
-            caller.wait_stream(es)
         starts = torch.empty((K, n), dtype=f32, device=dev)
         carry = torch.empty((n,), dtype=f32, device=dev)
         nat.check(nat.lib.lz_episode_starts(n, K, _p(done), _p(self.last_episode_starts),
                                             _p(starts), _p(carry), dev.index,
                                             ctypes.c_void_p(caller.cuda_stream)))
         self.last_episode_starts = carry
-        self._keep = (self.blob, self.last_obs, self.last_stack)  # alive until consumed
-        self.last_obs = obs_last
-        if stack_out is not None:
-            self.last_stack = stack_out
+        self._hand_over(obs_last, stack_out)
         if want_mom:
             if self.group is not None:
                 dist.all_reduce(mom, group=self.group)
@@ -991,7 +984,7 @@ class EvalResult:
         return float(self.err_scale * m.max().item())  # torch.max propagates NaN
 
 
-class FusedEvaluator:
+class FusedEvaluator(_PolicySeam):
     """The reference's evaluation loops on the device, one launch per evaluation
     (lz_evaluate_policy_f32 / _attn_f32 / _attn_stack_f32): K steps of {frozen
     VecNormalize, policy forward at SB3's float32 precision, (sample,) clip, env step}
@@ -1011,6 +1004,8 @@ class FusedEvaluator:
     frame_stack:   1 or 4 (VecFrameStack in front of the LayerNorm attention policy)
     """
 
+    _what = "evaluation"
+
     def __init__(self, backend, state_dict, obs_rms=None, clip_obs=10.0, norm_eps=1e-8,
                  deterministic=True, frame_stack=1):
         if backend.tdtype != torch.float32:
@@ -1023,50 +1018,19 @@ class FusedEvaluator:
         self.obs_rms, self.clip_obs, self.norm_eps = obs_rms, float(clip_obs), float(norm_eps)
         self.deterministic = bool(deterministic)
         self.act_low, self.act_high = action_bounds(backend.system_name)
-        self.frame_stack = int(frame_stack)
-        if self.frame_stack not in (1, 4):
-            raise ValueError("frame_stack must be 1 or 4 (the fused kernel's instantiations)")
-        if self.frame_stack > 1 and obs_rms is not None:
-            raise ValueError("the frame-stacked evaluation stacks raw observations (no VecNormalize)")
-        self.last_obs = None
-        self.last_stack = None
+        self._init_frame_stack(frame_stack)
         self.set_params(state_dict)
 
     def set_params(self, state_dict):
-        """Pack and upload the policy; the blob's format tag is checked on the host against
-        the launch this evaluator makes."""
-        self.attention = is_attention_policy(state_dict)
-        self.attention_ln = is_attention_ln_policy(state_dict)
-        if self.frame_stack > 1 and not self.attention_ln:
-            raise ValueError("frame_stack > 1 runs code/lorenz_filter/train.py's policy "
-                             "(the residual + LayerNorm attention extractor)")
-        if self.attention_ln:
-            if self.obs_rms is not None:
-                raise ValueError("the LayerNorm attention evaluation takes raw observations")
-            blob = pack_attn_ln_policy_f32(state_dict, self.frame_stack * self.O, self.A)
-        elif self.attention:
-            blob = pack_attn_policy_f32(state_dict, self.O, self.A)
-        else:
-            blob = pack_policy_f32(state_dict, self.O, self.A)
-        self._set_blob(blob)
-
-    def _set_blob(self, blob):
-        want = blob_format(self.attention, self.attention_ln, False)
-        got = int(nat.lib.lz_policy_blob_format(blob.ctypes.data, blob.size))
-        if got != want:
-            raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "policy blob format %d, the launch "
-                                     "expects %d" % (got, want))
-        self.blob = torch.from_numpy(blob).to(self.device)
+        """Pack and upload the policy (float32 only: no bf16 or i8x4 evaluation); the blob's
+        format tag is checked on the host against the launch this evaluator makes."""
+        self._select(state_dict)
+        self._set_blob(self._pack_params(state_dict, "fp32"))
 
     def reset(self, init=None):
         """VecEnv.reset() (init: injected initial states [N, init_dim], as lz_reset); the
         next evaluation starts from these observations and a fresh frame stack."""
-        obs = self.env.reset(init=init)
-        self.last_obs = obs.clone()
-        self.last_stack = torch.zeros((self.n, self.frame_stack * self.O), dtype=torch.float32,
-                                      device=self.device)
-        self.last_stack[:, -self.O:] = obs
-        return self.last_obs
+        return self._start_from(self.env.reset(init=init))
 
     def evaluate(self, K, skip=0, max_episodes=0, trace=None, trace_every=1, trace_start=0,
                  trace_state=False, trace_out=None, trace_slot_map=None):
@@ -1114,34 +1078,9 @@ class FusedEvaluator:
         e.act_low, e.act_high = self.act_low, self.act_high
         e.skip, e.max_episodes = int(skip), int(max_episodes)
         e.stats = _p(stats)
-        # the launch runs on the env handle's stream: order the caller's current stream
-        # (where blob / last_obs were written and the table is read) around it both ways
-        caller = torch.cuda.current_stream(dev)
-        es = self.env.stream
-        if es != caller:
-            es.wait_stream(caller)
-        stack_out = None
-        if self.attention_ln:
-            stack_out = torch.empty((n, self.frame_stack * O), dtype=torch.float32, device=dev)
-            stack = (self.frame_stack, _p(self.last_stack), _p(stack_out))
-            if tr is None:
-                nat.check(nat.lib.lz_evaluate_policy_attn_stack_f32(self.env._h, ctypes.byref(e), *stack))
-            else:
-                nat.check(nat.lib.lz_evaluate_policy_attn_stack_f32_trace(self.env._h, ctypes.byref(e), *stack,
-                                                                          ctypes.byref(tr)))
-        elif tr is None:
-            fn = nat.lib.lz_evaluate_policy_attn_f32 if self.attention else nat.lib.lz_evaluate_policy_f32
-            nat.check(fn(self.env._h, ctypes.byref(e)))
-        else:
-            fn = (nat.lib.lz_evaluate_policy_attn_f32_trace if self.attention
-                  else nat.lib.lz_evaluate_policy_f32_trace)
-            nat.check(fn(self.env._h, ctypes.byref(e), ctypes.byref(tr)))
-        if es != caller:
-            caller.wait_stream(es)
-        self._keep = (self.blob, self.last_obs, self.last_stack)  # alive until consumed
-        self.last_obs = obs_last
-        if stack_out is not None:
-            self.last_stack = stack_out
+        with self._on_env_stream():
+            stack_out = self._launch("evaluate" if tr is None else "trace", e, trace=tr)
+        self._hand_over(obs_last, stack_out)
         if tr is None:
             return EvalResult(stats, self.env.system_name)
         self._keep += (ids_dev, trace_slot_map)

@@ -62,17 +62,22 @@ def test_tag_bytes_are_where_the_header_says(pol):
 
 
 def test_collector_refuses_a_mismatched_blob(pol, monkeypatch):
-    """FusedRolloutCollector.set_params checks the packed blob's tag on the host before the
-    upload (a packer bug, or a blob swapped in by hand, never reaches a launch)."""
+    """FusedRolloutCollector.set_params and FusedEvaluator.set_params check the packed blob's
+    tag on the host before the upload (a packer bug, or a blob swapped in by hand, never
+    reaches a launch)."""
     mlp = pol.ActorCriticMlp(6, 2, seed=1).state_dict()
 
-    class Env:  # the collector needs only these before set_params packs
+    class Env:  # the two classes need only these before set_params packs
         num_envs, obs_dim, action_dim, system_name = 4, 6, 2, "pmsm"
         device = "cpu"
 
-    monkeypatch.setattr(pol, "pack_policy_f32", pol.pack_policy_i8x4)  # a wrong packer
-    col = pol.FusedRolloutCollector.__new__(pol.FusedRolloutCollector)
-    col.env, col.precision, col.frame_stack, col.obs_rms = Env, "fp32", 1, None
-    col.vecnorm_update, col.O, col.A, col.device, col.training = None, 6, 2, "cpu", True
-    with pytest.raises(nat.LorenzEnvError):
-        col.set_params(mlp)
+    _, size, tag = pol._PACKERS["mlp", "fp32"]  # a wrong packer behind the float32 row
+    monkeypatch.setitem(pol._PACKERS, ("mlp", "fp32"), (pol._PACKERS["mlp", "i8x4"][0], size, tag))
+    for cls in (pol.FusedRolloutCollector, pol.FusedEvaluator):
+        obj = cls.__new__(cls)
+        obj.env, obj.precision, obj.frame_stack, obj.obs_rms = Env, "fp32", 1, None
+        obj.vecnorm_update, obj.O, obj.A, obj.device, obj.training = None, 6, 2, "cpu", True
+        with pytest.raises(nat.LorenzEnvError, match="policy blob format %d, the launch expects %d"
+                           % (nat.BLOB_MLP_I8X4, nat.BLOB_MLP_F32)):
+            obj.set_params(mlp)
+        assert obj.blob is None  # refused before the upload
