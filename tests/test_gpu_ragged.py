@@ -4,8 +4,8 @@ The group's DMA sources are clamped to its own rows and the lanes past its envs 
 nothing (the noise-free systems, LZ_RAG = 2; PMSM / HR keep the staged path with a
 one-step register prefetch).  Bar: K fused steps == K lz_step calls bit for bit (obs,
 reward, done, the compact done list, every final state plane) for each kernel family
-whose last group is partial: one-wave (LORENZ3, PMSM, HR), split lanes (LORENZ3), lane
-pairs (PMSM), with TimeLimit truncations inside the launch.  (N not a multiple of 4 keeps the staged path:
+whose last group is partial: one-wave (LORENZ3 in both dtypes, T1, T2, PMSM, HR), split
+lanes (LORENZ3), lane pairs (PMSM), with TimeLimit truncations inside the launch.  (N not a multiple of 4 keeps the staged path:
 test_gpu_parity.py's 4,097 / 70,001 cases.)"""
 import numpy as np
 import pytest
@@ -28,21 +28,29 @@ def _np(t):
     return t.detach().cpu().numpy()
 
 
-@pytest.mark.parametrize("system,n,kernel", [
-    ("lorenz3", 16400, "rollout_wave"),   # 256 whole 64-env groups + 16 envs
-    ("lorenz3", 32784, "rollout_split"),  # 1,024 whole 32-env groups + 16
-    ("pmsm", 24592, "rollout_pair"),      # 768 whole pair groups + 16
-    ("pmsm", 4100, "rollout_wave"),       # + 4 envs
-    ("hr", 32784, "rollout_wave"),
-    ("hr", 1028, "rollout_wave"),
-])
-def test_ragged_group_full_path_equals_steps(gl, system, n, kernel):
+CASES = [
+    ("lorenz3", 16400, "rollout_wave", "float32"),   # 256 whole 64-env groups + 16 envs
+    ("lorenz3", 32784, "rollout_split", "float32"),  # 1,024 whole 32-env groups + 16
+    ("pmsm", 24592, "rollout_pair", "float32"),      # 768 whole pair groups + 16
+    ("pmsm", 4100, "rollout_wave", "float32"),       # + 4 envs
+    ("hr", 32784, "rollout_wave", "float32"),
+    ("hr", 1028, "rollout_wave", "float32"),
+    # kRag's other instantiations: T1 (A = 2: a narrower row-DMA clamp), T2, LORENZ3 double
+    ("transient1", 1000, "rollout_wave", "float32"),  # 15 whole groups + 40 envs
+    ("transient2", 1000, "rollout_wave", "float32"),
+    ("lorenz3", 1000, "rollout_wave", "float64"),
+]
+
+
+@pytest.mark.parametrize("system,n,kernel,dtype", CASES, ids=[
+    "%s-%d-%s%s" % (s, n, k, "" if d == "float32" else "-" + d) for s, n, k, d in CASES])
+def test_ragged_group_full_path_equals_steps(gl, system, n, kernel, dtype):
     from gym_lorenz import _native as nat
 
     K = 41
     kw = {"add_noise": True} if system in ("pmsm", "hr") else {}
-    a_be = gl.BatchedEnv(system, n, seed=21, max_episode_steps=13, **kw)
-    b_be = gl.BatchedEnv(system, n, seed=21, max_episode_steps=13, **kw)
+    a_be = gl.BatchedEnv(system, n, dtype=dtype, seed=21, max_episode_steps=13, **kw)
+    b_be = gl.BatchedEnv(system, n, dtype=dtype, seed=21, max_episode_steps=13, **kw)
     assert nat.launch_shape(a_be._h, nat.CALL_ROLLOUT)["kernel"] == kernel
     a_be.reset()
     b_be.reset()

@@ -162,7 +162,7 @@ def test_reset_draw_ranges(orc):
 
 # ----------------------------------------------------------------- legacy variants
 def _legacy_init(g, key):
-    return np.ascontiguousarray(g[key + "_init"], np.float64)
+    return np.array(g[key + "_init"], np.float64)  # a copy: the steps run in place, golden() is shared
 
 
 @pytest.mark.parametrize("key", ["t1", "t2", "tp", "sc"])
