@@ -13,7 +13,7 @@ from . import _native  # noqa: F401  (fails loudly if the native library is miss
 from .compat import HAVE_GYM, HAVE_GYMNASIUM, TimeLimit
 from .core import BatchedEnv
 from .envs import HRSyncEnv, LorenzDynamicEnv, PMSM_Sync_Env, lorenzEnv_transient
-from .policy import (EvalResult, EvalTrace, FusedA2C, FusedEvaluator, evaluate_policy,
+from .policy import (EvalResult, EvalTrace, FusedA2C, FusedEvaluator, FusedPPO, evaluate_policy,
                      linear_schedule)
 from .registry import SPECS, spec_for
 from .vec_env import LorenzVecEnv
@@ -62,4 +62,4 @@ _register()
 
 __all__ = ["BatchedEnv", "LorenzVecEnv", "HRSyncEnv", "PMSM_Sync_Env", "lorenzEnv_transient",
            "LorenzDynamicEnv", "make", "make_vec", "SPECS", "spec_for", "FusedEvaluator",
-           "EvalResult", "EvalTrace", "evaluate_policy", "FusedA2C", "linear_schedule"]
+           "EvalResult", "EvalTrace", "evaluate_policy", "FusedA2C", "FusedPPO", "linear_schedule"]

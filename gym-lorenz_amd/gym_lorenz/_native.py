@@ -216,6 +216,45 @@ class LzA2cApplyArgs(ctypes.Structure):
 A2C_STATS = ("policy_loss", "value_loss", "entropy_loss", "loss", "grad_norm", "clip_coef",
              "n_samples", "lr")
 
+
+class LzPpoGradArgs(ctypes.Structure):
+    """lz_ppo_grad_args (lz_ppo_grad_f32)."""
+    _fields_ = LzA2cGradArgs._fields_ + [
+        ("indices", ctypes.c_void_p),
+        ("n_rows", ctypes.c_int64),
+        ("old_log_prob", ctypes.c_void_p),
+        ("old_values", ctypes.c_void_p),
+        ("clip_range", ctypes.c_double),
+        ("clip_range_vf", ctypes.c_double),
+        ("adv_moments", ctypes.c_void_p),
+        ("ctrl", ctypes.c_void_p),
+    ]
+
+
+class LzAdamApplyArgs(ctypes.Structure):
+    """lz_adam_apply_args (lz_adam_apply_f32)."""
+    _fields_ = [
+        ("grad_sums", ctypes.c_void_p),
+        ("params", ctypes.c_void_p),
+        ("exp_avg", ctypes.c_void_p),
+        ("exp_avg_sq", ctypes.c_void_p),
+        ("n_params", ctypes.c_int64),
+        ("lr", ctypes.c_double),
+        ("max_grad_norm", ctypes.c_double),
+        ("beta1", ctypes.c_double),
+        ("beta2", ctypes.c_double),
+        ("eps", ctypes.c_double),
+        ("vf_coef", ctypes.c_double),
+        ("ent_coef", ctypes.c_double),
+        ("target_kl", ctypes.c_double),
+        ("ctrl", ctypes.c_void_p),
+        ("stats", ctypes.c_void_p),
+    ]
+
+
+# lz_adam_apply_f32's stats double [12]
+PPO_STATS = A2C_STATS + ("clip_fraction", "approx_kl", "step", "stopped")
+
 # columns of the evaluation table (lorenz_env.h LZ_EVAL_*): float64 [EVAL_COLS, N]
 (EVAL_ABS_SUM0, EVAL_SQ_SUM0, EVAL_MAX_ABS0) = 0, 4, 8
 (EVAL_N_WIN, EVAL_RET_SUM, EVAL_N_STEPS, EVAL_N_EP, EVAL_EP_RET_SUM, EVAL_EP_RET_SQ,
@@ -351,6 +390,12 @@ _SIGS = {
                                                 ctypes.c_int32]),
     "lz_a2c_grad_f32": (ctypes.c_int, [ctypes.POINTER(LzA2cGradArgs), ctypes.c_int32, VP]),
     "lz_a2c_apply_f32": (ctypes.c_int, [ctypes.POINTER(LzA2cApplyArgs), ctypes.c_int32, VP]),
+    "lz_ppo_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_int32]),
+    "lz_ppo_adv_moments": (ctypes.c_int, [VP, VP, ctypes.c_int64, ctypes.c_int64, VP, VP,
+                                          ctypes.c_int32, VP]),
+    "lz_ppo_grad_f32": (ctypes.c_int, [ctypes.POINTER(LzPpoGradArgs), ctypes.c_int32, VP]),
+    "lz_adam_apply_f32": (ctypes.c_int, [ctypes.POINTER(LzAdamApplyArgs), ctypes.c_int32, VP]),
     "lz_episode_starts": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, VP, VP, VP, VP,
                                          ctypes.c_int32, VP]),
     "lz_frame_stack": (ctypes.c_int, [VP, VP, VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,

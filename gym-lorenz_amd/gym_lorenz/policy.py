@@ -1318,3 +1318,282 @@ class FusedA2C:
             if callback is not None:
                 callback(self, batch, stats)
         return out
+
+
+# ------------------------------------------------------------------------------ PPO update
+# SB3 2.7.1 PPO.train() for the float32 MlpPolicy on the device (lz_ppo_adv_moments +
+# lz_ppo_grad_f32 + lz_adam_apply_f32 per minibatch): the update of code/train.py:97-129's,
+# code/lorenz_filter/train.py's and code/gym_run.py:83's learners.
+def _stream_ptr(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _check_indices(indices, n_rows, dev, who):
+    """(pointer or None, M) of a minibatch's row list: int32, on the device, contiguous,
+    at least one entry (its values are checked by the kernels, on the device)."""
+    if indices is None:
+        return None, n_rows
+    M = int(indices.numel()) if isinstance(indices, torch.Tensor) else 0
+    if M < 1:
+        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "%s: indices must be a non-empty tensor" % who)
+    return check_buffer(indices, "indices", torch.int32, M, dev), M
+
+
+def ppo_adv_moments(advantages, indices=None, out=None):
+    """lz_ppo_adv_moments on the current stream: float64 device tensor [2] = (mean, unbiased
+    std) of advantages[indices] (indices None: of all of them), in float64."""
+    dev = advantages.device
+    if dev.type != "cuda":
+        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "ppo_adv_moments: advantages must be a device tensor")
+    n_rows = int(advantages.numel())
+    adv = check_buffer(advantages, "advantages", torch.float32, n_rows, dev)
+    idx, M = _check_indices(indices, n_rows, dev, "ppo_adv_moments")
+    if out is None:
+        out = torch.empty((2,), dtype=torch.float64, device=dev)
+    o = check_buffer(out, "adv_moments", torch.float64, 2, dev)
+    nat.check(nat.lib.lz_ppo_adv_moments(adv, idx, M, n_rows, None, o, dev.index, _stream_ptr(dev)))
+    return out
+
+
+def ppo_grad(params, observations, actions, advantages, returns, old_log_prob, old_values, obs_dim,
+             act_dim, indices=None, clip_range=0.2, clip_range_vf=None, adv_moments=None, ctrl=None,
+             vf_coef=0.5, ent_coef=0.0, max_workgroups=0, workspace=None, out=None, hidden=HIDDEN):
+    """lz_ppo_grad_f32 on the current stream over the rows `indices` (int32 device tensor
+    [M]; None: every row) of the flat rollout arrays: float64 device tensor [P + 6] of the
+    gradient sums, then sum(policy loss terms), sum((ret - v_pred)^2), sum(-entropy), M,
+    the clipped count and sum((ratio - 1) - log_ratio).  adv_moments: ppo_adv_moments'
+    output (None: no normalisation); clip_range_vf None or <= 0: no value clipping
+    (old_values may then be None); ctrl: the int64 [2] control block of adam_apply.  Every
+    buffer is checked (core.check_buffer) before the launch."""
+    dev = params.device
+    O, A = int(obs_dim), int(act_dim)
+    if dev.type != "cuda":
+        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "ppo_grad: params must be a device tensor")
+    P = int(nat.lib.lz_a2c_param_count(O, A))
+    if P < 0:
+        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "ppo_grad: obs_dim must be 1..8, act_dim 1..4")
+    n_rows = int(advantages.numel())
+    cvf = 0.0 if clip_range_vf is None else float(clip_range_vf)
+    f32 = torch.float32
+    g = nat.LzPpoGradArgs()
+    g.params = check_buffer(params, "params", f32, P, dev)
+    g.observations = check_buffer(observations, "observations", f32, n_rows * O, dev)
+    g.actions = check_buffer(actions, "actions", f32, n_rows * A, dev)
+    g.advantages = check_buffer(advantages, "advantages", f32, n_rows, dev)
+    g.returns = check_buffer(returns, "returns", f32, n_rows, dev)
+    g.old_log_prob = check_buffer(old_log_prob, "old_log_prob", f32, n_rows, dev)
+    g.old_values = check_buffer(old_values, "old_values", f32, n_rows, dev, required=cvf > 0.0)
+    g.indices, M = _check_indices(indices, n_rows, dev, "ppo_grad")
+    g.n_samples, g.n_rows, g.obs_dim, g.act_dim, g.hidden = M, n_rows, O, A, int(hidden)
+    g.max_workgroups = int(max_workgroups)
+    g.vf_coef, g.ent_coef = float(vf_coef), float(ent_coef)
+    g.clip_range, g.clip_range_vf = float(clip_range), cvf
+    g.adv_moments = check_buffer(adv_moments, "adv_moments", torch.float64, 2, dev, required=False)
+    g.ctrl = check_buffer(ctrl, "ctrl", torch.int64, 2, dev, required=False)
+    need = int(nat.lib.lz_ppo_workspace_bytes(M, O, A, int(max_workgroups)))
+    if need < 0:
+        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "ppo_grad: empty batch or bad max_workgroups")
+    if workspace is None:
+        workspace = torch.empty((need // 8,), dtype=torch.float64, device=dev)
+    g.workspace = check_buffer(workspace, "workspace", torch.float64, need // 8, dev, at_least=True)
+    g.workspace_bytes = workspace.numel() * 8
+    if out is None:
+        out = torch.empty((P + 6,), dtype=torch.float64, device=dev)
+    g.grad_sums = check_buffer(out, "grad_sums", torch.float64, P + 6, dev)
+    nat.check(nat.lib.lz_ppo_grad_f32(ctypes.byref(g), dev.index, _stream_ptr(dev)))
+    return out
+
+
+def adam_apply(grad_sums, params, exp_avg, exp_avg_sq, ctrl, lr, max_grad_norm=0.5, betas=(0.9, 0.999),
+               eps=1e-5, vf_coef=0.5, ent_coef=0.0, target_kl=None, stats=None):
+    """lz_adam_apply_f32 on the current stream: the target_kl stop, clip_grad_norm_ and
+    torch.optim.Adam's step on params / exp_avg / exp_avg_sq in place, the step count and
+    the stop flag in ctrl (int64 device tensor [2] = step, stopped); returns the float64
+    device tensor stats [12] (_native.PPO_STATS)."""
+    dev = params.device
+    if dev.type != "cuda":
+        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "adam_apply: params must be a device tensor")
+    P = int(params.numel())
+    a = nat.LzAdamApplyArgs()
+    a.grad_sums = check_buffer(grad_sums, "grad_sums", torch.float64, P + 6, dev)
+    a.params = check_buffer(params, "params", torch.float32, P, dev)
+    a.exp_avg = check_buffer(exp_avg, "exp_avg", torch.float32, P, dev)
+    a.exp_avg_sq = check_buffer(exp_avg_sq, "exp_avg_sq", torch.float32, P, dev)
+    a.ctrl = check_buffer(ctrl, "ctrl", torch.int64, 2, dev)
+    a.n_params = P
+    a.lr, a.max_grad_norm, a.eps = float(lr), float(max_grad_norm), float(eps)
+    a.beta1, a.beta2 = float(betas[0]), float(betas[1])
+    a.vf_coef, a.ent_coef = float(vf_coef), float(ent_coef)
+    a.target_kl = 0.0 if target_kl is None else float(target_kl)
+    if stats is None:
+        stats = torch.empty((len(nat.PPO_STATS),), dtype=torch.float64, device=dev)
+    a.stats = check_buffer(stats, "stats", torch.float64, len(nat.PPO_STATS), dev)
+    nat.check(nat.lib.lz_adam_apply_f32(ctypes.byref(a), dev.index, _stream_ptr(dev)))
+    return stats
+
+
+class FusedPPO:
+    """SB3 PPO on a FusedRolloutCollector: ``learn`` is the loop collect(n_steps) ->
+    compute_returns_and_advantage -> train, and ``train`` one PPO.train(): n_epochs
+    permutations of the rollout's rows cut into minibatches of batch_size, each one
+    lz_ppo_adv_moments + lz_ppo_grad_f32 + lz_adam_apply_f32 on the device with no host
+    round trip (the Adam step count and the target_kl stop flag live on the device); the
+    per-minibatch stats come to the host once, and the new weights go through the host
+    packer into the collector's blob once, after the last minibatch.
+
+    learning_rate, clip_range (and clip_range_vf): a float or a schedule of SB3's
+    progress_remaining (linear_schedule).  generator: the torch.Generator (on the
+    collector's device) the permutations are drawn from.  Float32 MlpPolicy collectors only."""
+
+    def __init__(self, collector, state_dict, learning_rate=3e-4, n_steps=2048, batch_size=64,
+                 n_epochs=10, clip_range=0.2, clip_range_vf=None, normalize_advantage=True,
+                 ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, target_kl=None, generator=None):
+        if is_attention_policy(state_dict) or is_attention_ln_policy(state_dict):
+            raise ValueError("FusedPPO updates the MlpPolicy; the attention policies' update is "
+                             "not implemented")
+        if collector.precision in ("bf16", "i8x4"):
+            raise ValueError("FusedPPO needs a float32 collector (precision='fp32'), not %r"
+                             % collector.precision)
+        if collector.frame_stack != 1:
+            raise ValueError("FusedPPO updates the MlpPolicy (frame_stack=1)")
+        if int(batch_size) < 1 or int(n_epochs) < 1 or int(n_steps) < 1:
+            raise ValueError("FusedPPO: n_steps, batch_size and n_epochs must be >= 1")
+        if normalize_advantage and int(batch_size) < 2:
+            raise ValueError("FusedPPO: batch_size must be > 1 with normalize_advantage "
+                             "(SB3 asserts it)")
+        self.collector = collector
+        self.device = collector.device
+        self.O, self.A = collector.O, collector.A
+        self.layout, self.P = a2c_param_layout(self.O, self.A)
+        flat = []
+        for k, (_, shp) in self.layout.items():
+            if k not in state_dict:
+                raise KeyError("policy state_dict lacks %r" % k)
+            t = torch.as_tensor(_np(state_dict[k]))
+            if tuple(t.shape) != tuple(shp):
+                raise ValueError("%s has shape %s, expected %s (FusedPPO implements hidden=%d)"
+                                 % (k, tuple(t.shape), shp, HIDDEN))
+            flat.append(t.reshape(-1))
+        dev = self.device
+        self.params = torch.cat(flat).to(dev).contiguous()
+        self.exp_avg = torch.zeros_like(self.params)
+        self.exp_avg_sq = torch.zeros_like(self.params)
+        self.ctrl = torch.zeros((2,), dtype=torch.int64, device=dev)  # Adam's step, stopped
+        self.learning_rate, self.clip_range, self.clip_range_vf = learning_rate, clip_range, clip_range_vf
+        self.n_steps, self.batch_size, self.n_epochs = int(n_steps), int(batch_size), int(n_epochs)
+        self.normalize_advantage = bool(normalize_advantage)
+        self.vf_coef, self.ent_coef = float(vf_coef), float(ent_coef)
+        self.max_grad_norm = float(max_grad_norm)
+        self.target_kl = None if target_kl is None else float(target_kl)
+        self.generator = generator
+        self.num_timesteps = 0
+        self.n_updates = 0
+        self.progress_remaining = 1.0
+        self._sums = torch.empty((self.P + 6,), dtype=torch.float64, device=dev)
+        self._mom = torch.empty((2,), dtype=torch.float64, device=dev)
+        self._ws = self._perm = self._stats = None
+        collector.set_params(self.state_dict())
+
+    def _now(self, v):
+        return float(v(self.progress_remaining)) if callable(v) else float(v)
+
+    def _lr(self):
+        return self._now(self.learning_rate)
+
+    def state_dict(self):
+        """SB3 keys -> float32 CPU tensors (one device-to-host copy)."""
+        return self._by_key(self.params)
+
+    def _by_key(self, vec):
+        flat = vec.detach().cpu()
+        return {k: flat[o:o + int(np.prod(shp))].reshape(shp).clone()
+                for k, (o, shp) in self.layout.items()}
+
+    def optimizer_state(self):
+        """{"exp_avg": {SB3 key: float32 CPU tensor}, "exp_avg_sq": {...}, "step": int}:
+        torch.optim.Adam's state."""
+        return {"exp_avg": self._by_key(self.exp_avg), "exp_avg_sq": self._by_key(self.exp_avg_sq),
+                "step": int(self.ctrl[0].item())}
+
+    def minibatches(self, B):
+        """[(first, last)] positions of a permutation of B rows that form each minibatch
+        (RolloutBuffer.get: the last one may be shorter)."""
+        return [(s, min(s + self.batch_size, B)) for s in range(0, B, self.batch_size)]
+
+    def train(self, batch, lr=None, clip_range=None):
+        """One PPO.train() on the RolloutBatch (advantages / returns set by
+        compute_returns_and_advantage); pushes the new weights to the collector.  Returns
+        {"rows": float64 array [n_epochs * n_minibatches, 12] (_native.PPO_STATS per
+        minibatch), SB3's logged means over the minibatches whose loss was computed
+        (policy_gradient_loss, value_loss, entropy_loss, clip_fraction, approx_kl), loss (the
+        last one computed), learning_rate, clip_range, stopped, n_updates}."""
+        if batch.advantages is None or batch.returns is None:
+            raise ValueError("FusedPPO.train: compute_returns_and_advantage(batch) first")
+        lr = self._lr() if lr is None else float(lr)
+        clip = self._now(self.clip_range) if clip_range is None else float(clip_range)
+        cvf = None if self.clip_range_vf is None else self._now(self.clip_range_vf)
+        dev = self.device
+        B = int(batch.advantages.numel())
+        cuts = self.minibatches(B)
+        need = int(nat.lib.lz_ppo_workspace_bytes(min(self.batch_size, B), self.O, self.A, 0)) // 8
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty((max(need, 1),), dtype=torch.float64, device=dev)
+        if self._perm is None or self._perm.numel() != B:
+            self._perm = torch.empty((B,), dtype=torch.int32, device=dev)
+        rows = self.n_epochs * len(cuts)
+        if self._stats is None or self._stats.shape[0] != rows:
+            self._stats = torch.empty((rows, len(nat.PPO_STATS)), dtype=torch.float64, device=dev)
+        self.ctrl[1:].zero_()  # SB3's continue_training = True (a fill: capturable)
+        i = 0
+        for _ in range(self.n_epochs):
+            torch.randperm(B, dtype=torch.int32, device=dev, generator=self.generator, out=self._perm)
+            for lo, hi in cuts:
+                self.minibatch_step(batch, self._perm[lo:hi], lr, clip, cvf, self._stats[i])
+                i += 1
+        out = self._stats.cpu().numpy()
+        self.collector.set_params(self.state_dict())
+        self.n_updates += self.n_epochs
+        col = nat.PPO_STATS.index
+        done = out[~np.isnan(out[:, col("n_samples")])]  # after a stop the rows hold no losses
+        mean = (lambda name: float(done[:, col(name)].mean())) if len(done) else (lambda name: float("nan"))
+        return {"rows": out, "policy_gradient_loss": mean("policy_loss"), "value_loss": mean("value_loss"),
+                "entropy_loss": mean("entropy_loss"), "clip_fraction": mean("clip_fraction"),
+                "approx_kl": mean("approx_kl"), "loss": float(done[-1, col("loss")]) if len(done) else float("nan"),
+                "learning_rate": lr, "clip_range": clip, "stopped": bool(out[-1, col("stopped")] != 0),
+                "n_updates": self.n_updates}
+
+    def minibatch_step(self, batch, indices, lr, clip_range, clip_range_vf, stats_row):
+        """moments -> grad -> apply for the minibatch of rows `indices`; nothing leaves the
+        device, and after a train() of the same batch_size nothing is allocated (the three
+        launches capture into a graph)."""
+        M = int(indices.numel())
+        mom = None
+        if self.normalize_advantage and M > 1:  # SB3: len(advantages) > 1
+            mom = ppo_adv_moments(batch.advantages, indices, out=self._mom)
+        ppo_grad(self.params, batch.observations, batch.actions, batch.advantages, batch.returns,
+                 batch.log_probs, batch.values, self.O, self.A, indices, clip_range, clip_range_vf, mom,
+                 self.ctrl, self.vf_coef, self.ent_coef, workspace=self._ws, out=self._sums)
+        adam_apply(self._sums, self.params, self.exp_avg, self.exp_avg_sq, self.ctrl, lr,
+                   self.max_grad_norm, (0.9, 0.999), 1e-5, self.vf_coef, self.ent_coef, self.target_kl,
+                   stats=stats_row)
+
+    def learn(self, total_timesteps, callback=None):
+        """SB3 OnPolicyAlgorithm.learn: rollouts of n_steps x num_envs timesteps until
+        total_timesteps, progress_remaining = 1 - num_timesteps / total_timesteps updated
+        after each collect (what the schedules see in train()); gamma and gae_lambda are
+        the collector's.  callback(self, batch, stats) runs after every train().  Returns the
+        list of the updates' stats."""
+        total = int(total_timesteps)
+        col = self.collector
+        out = []
+        start = self.num_timesteps
+        while self.num_timesteps - start < total:
+            batch = col.collect(self.n_steps)
+            self.num_timesteps += self.n_steps * col.n
+            self.progress_remaining = 1.0 - float(self.num_timesteps - start) / float(total)
+            col.compute_returns_and_advantage(batch)
+            stats = self.train(batch)
+            out.append(stats)
+            if callback is not None:
+                callback(self, batch, stats)
+        return out

@@ -50,6 +50,10 @@
  *   lz_a2c_grad_f32 / lz_a2c_apply_f32 (lz_a2c_workspace_bytes, lz_a2c_param_count)
  *       -> SB3 A2C.train() for those MlpPolicy learners: one gradient step on the whole
  *          rollout, clip_grad_norm_ and RMSpropTFLike (code/lorenz_pmsm/train.py:151-185)
+ *   lz_ppo_adv_moments / lz_ppo_grad_f32 / lz_adam_apply_f32 (lz_ppo_workspace_bytes)
+ *       -> SB3 PPO.train() for the MlpPolicy: one clipped minibatch step, advantage
+ *          normalisation, clip_grad_norm_ and Adam, the target_kl stop (code/train.py:97-129,
+ *          code/lorenz_filter/train.py, code/gym_run.py:83)
  *   lz_attn_policy_pack / lz_rollout_policy_attn
  *       -> the same for code/train.py:52-112 and code/gym_try.py:52-116 (PPO with the
  *          AttentionFeaturesExtractor)
@@ -816,6 +820,123 @@ int64_t lz_a2c_workspace_bytes(int64_t n_samples, int32_t obs_dim, int32_t act_d
                                int32_t max_workgroups);
 lz_status lz_a2c_grad_f32(const lz_a2c_grad_args* g, int32_t device, void* hip_stream);
 lz_status lz_a2c_apply_f32(const lz_a2c_apply_args* a, int32_t device, void* hip_stream);
+
+/* ------------------------------------------------------------------------------
+ * One PPO minibatch step for the same float32 MlpPolicy: SB3 2.7.1 PPO.train()
+ * (ppo/ppo.py:181-300) as the reference's PPO learners run it (code/train.py:97-129: PPO,
+ * n_steps=2048, batch_size=64, gae_lambda=0.95, lr=3e-4; code/lorenz_filter/train.py;
+ * code/gym_run.py:83).  For each of n_epochs SB3 draws a permutation of the B = K*N rollout
+ * rows and cuts it into minibatches of batch_size (RolloutBuffer.get, common/buffers.py; the
+ * last one may be shorter); for a minibatch of M rows, with log_prob / entropy / v from
+ * ActorCriticPolicy.evaluate_actions and DiagGaussianDistribution as above:
+ *   adv_n  = (adv - mean(adv)) / (std(adv) + 1e-8)   if normalize_advantage and M > 1
+ *   ratio  = exp(log_prob - old_log_prob)
+ *   pl_i   = -min(adv_n ratio, adv_n clamp(ratio, 1 - clip_range, 1 + clip_range))
+ *   v_pred = v, or old_v + clamp(v - old_v, -clip_range_vf, +clip_range_vf)
+ *   loss   = mean(pl_i) + vf_coef mean((ret - v_pred)^2) + ent_coef (-mean(entropy))
+ *   clip_fraction = mean(|ratio - 1| > clip_range);  approx_kl = mean((ratio - 1) - log_ratio)
+ * then, unless target_kl is set and approx_kl > 1.5 target_kl (SB3 stops: no optimizer step
+ * for this minibatch nor for the rest of this train()), clip_grad_norm_(max_grad_norm) and
+ * torch.optim.Adam(betas=(0.9, 0.999), eps=1e-5 -- ActorCriticPolicy's optimizer_kwargs --
+ * no weight decay, no amsgrad).  The derivative of the surrogate is torch autograd's: sample
+ * i contributes d pl_i / d log_prob = -adv_n ratio unless (ratio > 1 + clip and adv_n > 0) or
+ * (ratio < 1 - clip and adv_n < 0), where it contributes 0 (the clip edges are active); the
+ * value term contributes 0 where |v - old_v| > clip_range_vf (the edge is active).
+ *
+ * The flat arrays (observations [n_rows, O], actions [n_rows, A], advantages, returns,
+ * old_log_prob, old_values [n_rows]) are the collector's time-major [K, N] rollout buffers;
+ * SB3 flattens env-major (swap_and_flatten), which a uniform permutation of the rows does
+ * not see.  Sample i of the minibatch is row indices[i] (indices NULL: row i).  A row
+ * outside [0, n_rows) is never dereferenced: that sample adds nothing to the gradient and
+ * makes the three loss sums (and lz_ppo_adv_moments' outputs) NaN.
+ *
+ * lz_ppo_adv_moments (replaces advantages.mean() / advantages.std() of ppo.py:217-218)
+ * writes out double [2] = {mean, unbiased std} of the minibatch's advantages: float64
+ * throughout, two passes (the mean, then the centred squares), fixed-order partial sums
+ * with their rounding errors carried along, one workgroup, no atomics: the same bits from
+ * the same inputs.  workspace is not used by this one-workgroup form and may be NULL.
+ * lz_ppo_grad_f32 rounds both to float32 and forms (adv - mean) / (std + 1e-8f) in float32,
+ * as torch does on its float32 tensors.  With M == 1 pass adv_moments NULL (SB3's
+ * len(advantages) > 1).  Refused before any HIP call: NULL advantages or out, n_samples <
+ * 1, n_rows < 1, indices NULL with n_samples > n_rows (LZ_ERR_INVALID).
+ *
+ * lz_ppo_grad_f32 (replaces ppo.py:205-262, the forward, the loss and loss.backward())
+ * writes grad_sums double [P + 6]: the P gradient SUMS over the samples, then sum(pl_i),
+ * sum((ret - v_pred)^2), sum(-entropy), the count M, sum(|ratio - 1| > clip_range) and
+ * sum((ratio - 1) - log_ratio) -- sums, not means, so a multi-GPU learner all-reduces the
+ * vector exactly as it does A2C's.  The arithmetic, the slots, the fixed-order reduction and
+ * the determinism are lz_a2c_grad_f32's; expf is the accurate one.  With ctrl non-NULL and
+ * ctrl[1] (stopped) set, the two kernels return at entry and grad_sums keeps what it held.
+ * Refused before any HIP call: what lz_a2c_grad_f32 refuses, NULL old_log_prob, NULL
+ * old_values with clip_range_vf > 0, n_rows < 1, indices NULL with n_samples > n_rows, a
+ * clip_range that is negative or not finite, a clip_range_vf that is not finite, a workspace
+ * smaller than lz_ppo_workspace_bytes (LZ_ERR_INVALID); hidden != 128 (LZ_ERR_UNSUPPORTED).
+ *
+ * lz_adam_apply_f32 (replaces ppo.py:264-282: the target_kl break, clip_grad_norm_,
+ * optimizer.step()) takes grad_sums and the control block ctrl int64 [2] = {step, stopped}
+ * on the device and, in float64 from the float32 state:
+ *   if stopped: nothing.  if target_kl > 0 and approx_kl > 1.5 target_kl: stopped = 1, nothing.
+ *   g = float32(grad_sums[i] / count);  coef = min(1, max_grad_norm / (||g||_2 + 1e-6))
+ *   t = step + 1;  m = beta1 m + (1 - beta1) coef g;  v = beta2 v + (1 - beta2) (coef g)^2
+ *   p = p - (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps);  step = t
+ * rounding p, m and v once into the float32 params, exp_avg and exp_avg_sq, in place (the
+ * caller initialises both moments and ctrl to zero and clears ctrl[1] at the start of each
+ * train()).  The step count lives on the device so that a whole update can be captured in
+ * a graph once and replayed.  stats double [12]: policy loss, value loss, entropy loss,
+ * loss, gradient norm before clipping, clip coefficient, count, lr, clip_fraction,
+ * approx_kl, step after the call, stopped.  The minibatch that sets the flag reports its
+ * losses, clip_fraction and approx_kl with NaN for the norm and the coefficient; a later one
+ * (whose gradient was never computed) reports NaN for everything but lr, step and stopped.
+ * Refused before any HIP call: NULL pointers, n_params < 1, a beta outside [0, 1)
+ * (LZ_ERR_INVALID).  All three: no allocation, no host synchronisation, graph-capturable.
+ * ------------------------------------------------------------------------------ */
+typedef struct lz_ppo_grad_args {
+  const float* params;        /* [P] (lz_a2c_param_count, the layout above) */
+  const float* observations;  /* [n_rows, O] */
+  const float* actions;       /* [n_rows, A] the unclipped samples */
+  const float* advantages;    /* [n_rows] */
+  const float* returns;       /* [n_rows] */
+  int64_t n_samples;          /* M >= 1 */
+  int32_t obs_dim;            /* 1..8 */
+  int32_t act_dim;            /* 1..4 */
+  int32_t hidden;             /* 128 */
+  int32_t max_workgroups;     /* as lz_a2c_grad_args */
+  double vf_coef, ent_coef;
+  void* workspace;            /* device, >= lz_ppo_workspace_bytes(...) bytes */
+  int64_t workspace_bytes;
+  double* grad_sums;          /* [P + 6] out */
+  const int32_t* indices;     /* [M] rows of the minibatch, NULL: rows 0 .. M-1 */
+  int64_t n_rows;             /* rows of the flat arrays (K*N) */
+  const float* old_log_prob;  /* [n_rows] RolloutBatch.log_probs */
+  const float* old_values;    /* [n_rows] RolloutBatch.values; may be NULL without value clipping */
+  double clip_range;
+  double clip_range_vf;       /* <= 0: none */
+  const double* adv_moments;  /* device [2] from lz_ppo_adv_moments, NULL: no normalisation */
+  const int64_t* ctrl;        /* device {step, stopped}, NULL: never return early */
+} lz_ppo_grad_args;
+
+typedef struct lz_adam_apply_args {
+  const double* grad_sums;    /* [P + 6] */
+  float* params;              /* [P] in place */
+  float* exp_avg;             /* [P] in place */
+  float* exp_avg_sq;          /* [P] in place */
+  int64_t n_params;           /* P */
+  double lr, max_grad_norm, beta1, beta2, eps;
+  double vf_coef, ent_coef;   /* for stats[3] only */
+  double target_kl;           /* <= 0: none */
+  int64_t* ctrl;              /* device {step, stopped} in place */
+  double* stats;              /* [12] out */
+} lz_adam_apply_args;
+
+/* The workspace bytes a lz_ppo_grad_f32 call with these arguments needs, -1 if it would
+ * refuse them.  Host-only. */
+int64_t lz_ppo_workspace_bytes(int64_t n_samples, int32_t obs_dim, int32_t act_dim,
+                               int32_t max_workgroups);
+lz_status lz_ppo_adv_moments(const float* advantages, const int32_t* indices, int64_t n_samples,
+                             int64_t n_rows, void* workspace, double* out, int32_t device,
+                             void* hip_stream);
+lz_status lz_ppo_grad_f32(const lz_ppo_grad_args* g, int32_t device, void* hip_stream);
+lz_status lz_adam_apply_f32(const lz_adam_apply_args* a, int32_t device, void* hip_stream);
 
 /* RolloutBuffer.episode_starts of one collect (SB3 2.7.1 OnPolicyAlgorithm.
  * collect_rollouts: rollout_buffer.add(..., self._last_episode_starts, ...), then
