@@ -9,70 +9,23 @@
 // rmsprop_tf_like.py: square_avg starts at ones, eps inside the root) as the reference's
 // learner uses them (code/lorenz_pmsm/train.py:151-185).
 //
-// Dataflow of k_a2c_grad (one net per workgroup: pi on the even, vf on the odd workgroups;
-// 4 waves; a tile = 32 samples; grid-stride over the tiles).  Every matrix of a tile lives
-// in LDS as a [unit][sample] image with row stride 33 (any row or column of 32 is then
-// conflict-free), and wave w owns unit tile w (32 units) of every product on
-// v_mfma_f32_32x32x2_f32 (A[i = lane & 31][k = lane >> 5], B[k = lane >> 5][j = lane & 31],
-// D[i = (g & 3) + 8 (g >> 2) + 4 (lane >> 5)][j = lane & 31] in register g):
-//   h1 = tanh(W1 x + b1)            A = W1 (LDS [unit][8], zero padded), B = x [k][sample]
-//   h2 = tanh(W2 h1 + b2)           A = W2 rows (LDS, row stride 129),  B = h1 image
-//   out = W_head h2 + b_head        each wave's 32 units from its registers, the four
-//                                   partial sums added in wave order
-//   d_out per sample                (-adv (a - mu) / sigma^2 | -2 vf_coef (ret - v)); 0 for
-//                                   lanes past the last sample, whose x is 0 too
-//   d2 = (W_head^T d_out) (1 - h2^2)    in the registers that hold h2
-//   d1 = (W2^T d2) (1 - h1^2)       A = W2 columns (the same LDS image), B = d2 image
-//   dW2 += d2 h1^T                  A = d2 image [unit][sample], B = h1 image read along
-//                                   the sample: wave w accumulates rows 32 w .. 32 w + 31
-//                                   of dW2 (4 accumulator tiles) over all the workgroup's
-//                                   samples
-//   dW1, db1, db2, dW_head          sample sums by one thread per unit over the images
-//   db_head, dlog_std, the loss sums  float64 per lane, reduced once at the end
-// The float32 accumulators are added into the workgroup's float64 partial vector (its own
-// slot of the workspace, no atomics) every kFlushTiles tiles, so no float32 chain is longer
-// than 2048 samples whatever the batch; k_a2c_reduce adds the slots in slot order.  Two
-// launches on the same inputs give the same bits.
+// k_a2c_grad is lz_grad_body.inc with LZ_GRAD_PPO 0 (the dataflow is described there; the
+// same text with LZ_GRAD_PPO 1 is lz_ppo.hip's k_ppo_grad).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 
+#include "lz_grad_common.h"
 #include "lz_internal.h"
 
 namespace lz {
 namespace a2c {
 
-typedef float v16 __attribute__((ext_vector_type(16)));
+using namespace grad;
 
-constexpr int kH = 128;          // hidden units (LZ_POLICY_HIDDEN)
-constexpr int kTile = 32;        // samples per workgroup tile
-constexpr int kLd = 33;          // row stride of the [unit][sample] images
-constexpr int kW2Ld = 129;       // row stride of the W2 image
-constexpr int kMaxO = 8, kMaxA = 4;
-constexpr int kFlushTiles = 64;  // float32 chains end after 64 * 32 samples
-constexpr int kDefaultWgs = 128; // workgroups per net when the caller sets no cap
-constexpr int kMaxWgs = 4096;
-
-// offsets of the 13 tensors (gym_lorenz.policy.KEYS order, nn.Linear layout) in the flat
-// parameter vector, and its length
-struct Layout {
-  int64_t off[13];
-  int64_t P;
-};
-
-__host__ __device__ inline Layout layout(int O, int A) {
-  Layout L;
-  const int64_t n[13] = {(int64_t)kH * O, kH, (int64_t)kH * kH, kH, (int64_t)kH * O, kH,
-                         (int64_t)kH * kH, kH, (int64_t)A * kH, A, kH, 1, A};
-  int64_t o = 0;
-  for (int i = 0; i < 13; ++i) {
-    L.off[i] = o;
-    o += n[i];
-  }
-  L.P = o;
-  return L;
-}
+constexpr int kTail = 4;      // loss sums and the count after the P gradient sums
+constexpr int kLaneSums = 2;  // policy / value loss sum, entropy sum
 
 struct GradArgs {
   const float* params;
@@ -86,313 +39,11 @@ struct GradArgs {
   double* part;  // [workgroups per net][P + 4]
 };
 
-__device__ __forceinline__ int acc_row(int g, int h) { return (g & 3) + 8 * (g >> 2) + 4 * h; }
-
-__device__ __forceinline__ v16 mfma(float a, float b, v16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void put(double* p, float v, bool first) {
-  *p = first ? (double)v : *p + (double)v;
-}
-
-__global__ __launch_bounds__(256) void k_a2c_grad(GradArgs a) {
-  __shared__ float sW2[kH * kW2Ld];
-  __shared__ float sW1[kH * kMaxO];
-  __shared__ float sB1[kH], sB2[kH];
-  __shared__ float sWh[kMaxA * kH];
-  __shared__ float sX[kMaxO * kTile];
-  __shared__ float sH1[kH * kLd], sH2[kH * kLd], sD2[kH * kLd], sD1[kH * kLd];
-  __shared__ float sHP[4 * kMaxA * kTile];
-  __shared__ float sDO[kMaxA * kTile];
-  __shared__ double sRed[kTile * (2 + 2 * kMaxA)];
-
-  const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
-  const bool pi = (blockIdx.x & 1u) == 0;
-  const int wg = (int)(blockIdx.x >> 1), nwg = (int)(gridDim.x >> 1);
-  const int O = a.O, A = a.A, NH = pi ? A : 1;
-  const Layout L = layout(O, A);
-  // (selected, not indexed: a runtime index would put the table in scratch)
-  const int64_t oW1 = pi ? L.off[0] : L.off[4], oB1 = pi ? L.off[1] : L.off[5];
-  const int64_t oW2 = pi ? L.off[2] : L.off[6], oB2 = pi ? L.off[3] : L.off[7];
-  const int64_t oWh = pi ? L.off[8] : L.off[10], oBh = pi ? L.off[9] : L.off[11];
-  const int64_t oLs = L.off[12], P = L.P;
-  const float* gW1 = a.params + oW1;
-  const float* gB1 = a.params + oB1;
-  const float* gW2 = a.params + oW2;
-  const float* gB2 = a.params + oB2;
-  const float* gWh = a.params + oWh;
-  const float* gBh = a.params + oBh;
-  const float* gLs = a.params + oLs;
-
-  for (int e = tid; e < kH * kH; e += 256) sW2[(e >> 7) * kW2Ld + (e & 127)] = gW2[e];
-  for (int e = tid; e < kH * kMaxO; e += 256) {
-    const int u = e >> 3, k = e & 7;
-    sW1[e] = k < O ? gW1[u * O + k] : 0.0f;
-  }
-  for (int e = tid; e < kH; e += 256) {
-    sB1[e] = gB1[e];
-    sB2[e] = gB2[e];
-  }
-  for (int e = tid; e < kMaxA * kH; e += 256) sWh[e] = e < NH * kH ? gWh[e] : 0.0f;
-  for (int e = tid; e < kMaxA * kTile; e += 256) sDO[e] = 0.0f;
-  float bh[kMaxA], ls[kMaxA], inv_var[kMaxA];
-#pragma unroll
-  for (int j = 0; j < kMaxA; ++j) {
-    bh[j] = j < NH ? gBh[j] : 0.0f;
-    ls[j] = (pi && j < A) ? gLs[j] : 0.0f;
-    const float sd = expf(ls[j]);
-    inv_var[j] = 1.0f / (sd * sd);
-  }
-  __syncthreads();
-
-  v16 accW2[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int g = 0; g < 16; ++g) accW2[t][g] = 0.0f;
-  float accS[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) accS[i] = 0.0f;
-  double lossS = 0.0, entS = 0.0, cntS = 0.0, dbh[kMaxA], dls[kMaxA];
-#pragma unroll
-  for (int j = 0; j < kMaxA; ++j) dbh[j] = dls[j] = 0.0;
-
-  double* slot = a.part + (int64_t)wg * (P + 4);
-  bool first = true;
-  int since = 0;
-
-  // the workgroup's float32 accumulators into its float64 slot, then zeroed
-  auto flush = [&]() __attribute__((always_inline)) {
-    double* pW2 = slot + oW2;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        put(pW2 + (32 * w + acc_row(g, h)) * kH + 32 * t + r, accW2[t][g], first);
-        accW2[t][g] = 0.0f;
-        // eight read-modify-writes in flight at a time, not all 64 (registers)
-        if ((g & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-      }
-    if (tid < kH) {
-#pragma unroll
-      for (int o = 0; o < kMaxO; ++o)
-        if (o < O) put(slot + oW1 + tid * O + o, accS[o], first);
-      put(slot + oB1 + tid, accS[8], first);
-    } else {
-      const int u = tid - kH;
-      put(slot + oB2 + u, accS[8], first);
-#pragma unroll
-      for (int j = 0; j < kMaxA; ++j)
-        if (j < NH) put(slot + oWh + j * kH + u, accS[j], first);
-    }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) accS[i] = 0.0f;
-    first = false;
-    since = 0;
-  };
-
-  const int64_t ntiles = (a.n + kTile - 1) / kTile;
-  for (int64_t tile = wg; tile < ntiles; tile += nwg) {
-    const int64_t base = tile * kTile;
-    {  // x as [k][sample]; rows k >= O and samples past the end are 0
-      const int k = tid >> 5, s = tid & 31;
-      const int64_t i = base + s;
-      sX[k * kTile + s] = (k < O && i < a.n) ? a.obs[i * O + k] : 0.0f;
-    }
-    const int64_t si = base + r;
-    const bool valid = si < a.n;
-    __syncthreads();
-
-    // layer 1
-    v16 c, h1, h2;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) c[g] = sB1[32 * w + acc_row(g, h)];
-#pragma unroll
-    for (int st = 0; st < kMaxO / 2; ++st)
-      c = mfma(sW1[(32 * w + r) * kMaxO + 2 * st + h], sX[(2 * st + h) * kTile + r], c);
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      h1[g] = tanhf(c[g]);
-      sH1[(32 * w + acc_row(g, h)) * kLd + r] = h1[g];
-    }
-    __syncthreads();
-
-    // layer 2
-#pragma unroll
-    for (int g = 0; g < 16; ++g) c[g] = sB2[32 * w + acc_row(g, h)];
-#pragma unroll 8
-    for (int st = 0; st < kH / 2; ++st)
-      c = mfma(sW2[(32 * w + r) * kW2Ld + 2 * st + h], sH1[(2 * st + h) * kLd + r], c);
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      h2[g] = tanhf(c[g]);
-      sH2[(32 * w + acc_row(g, h)) * kLd + r] = h2[g];
-    }
-    // this wave's share of the head rows
-#pragma unroll
-    for (int j = 0; j < kMaxA; ++j) {
-      if (j < NH) {
-        float p = 0.0f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) p = fmaf(sWh[j * kH + 32 * w + acc_row(g, h)], h2[g], p);
-        p += __shfl_xor(p, 32, 64);
-        if (h == 0) sHP[(w * kMaxA + j) * kTile + r] = p;
-      }
-    }
-    __syncthreads();
-
-    // heads, the loss terms and d_out of sample r (every wave computes the same values)
-    float dout[kMaxA];
-    {
-      float out[kMaxA];
-#pragma unroll
-      for (int j = 0; j < kMaxA; ++j) {
-        out[j] = 0.0f;
-        if (j < NH)
-          out[j] = (((sHP[(0 * kMaxA + j) * kTile + r] + sHP[(1 * kMaxA + j) * kTile + r]) +
-                     sHP[(2 * kMaxA + j) * kTile + r]) + sHP[(3 * kMaxA + j) * kTile + r]) + bh[j];
-        dout[j] = 0.0f;
-      }
-      const bool own = valid && w == 0 && h == 0;
-      if (pi) {
-        const float adv = valid ? a.adv[si] : 0.0f;
-        float logp = 0.0f;
-#pragma unroll
-        for (int j = 0; j < kMaxA; ++j) {
-          if (j < A) {
-            const float act = valid ? a.act[si * A + j] : 0.0f;
-            const float diff = act - out[j];
-            const float q = diff * diff * inv_var[j];
-            logp += (-0.5f * q - ls[j]) - 0.91893853320467274f;
-            dout[j] = valid ? -adv * (diff * inv_var[j]) : 0.0f;
-            if (own) {
-              dbh[j] += (double)dout[j];
-              dls[j] += (double)(-adv * (q - 1.0f) - a.ent_coef);
-            }
-          }
-        }
-        if (own) {
-          lossS += (double)(-adv * logp);
-          float ent = 0.0f;
-#pragma unroll
-          for (int j = 0; j < kMaxA; ++j)
-            if (j < A) ent += 1.4189385332046727f + ls[j];
-          entS += (double)(-ent);
-          cntS += 1.0;
-        }
-      } else {
-        const float ret = valid ? a.ret[si] : 0.0f;
-        const float e = ret - out[0];
-        dout[0] = valid ? -2.0f * a.vf_coef * e : 0.0f;
-        if (own) {
-          dbh[0] += (double)dout[0];
-          lossS += (double)(e * e);
-        }
-      }
-      if (w == 0 && h == 0) {
-#pragma unroll
-        for (int j = 0; j < kMaxA; ++j)
-          if (j < NH) sDO[j * kTile + r] = dout[j];
-      }
-    }
-    // d2 in place of h2
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      const int u = 32 * w + acc_row(g, h);
-      float cc = 0.0f;
-#pragma unroll
-      for (int j = 0; j < kMaxA; ++j)
-        if (j < NH) cc = fmaf(sWh[j * kH + u], dout[j], cc);
-      sD2[u * kLd + r] = cc * (1.0f - h2[g] * h2[g]);
-    }
-    __syncthreads();
-
-    // d1 = (W2^T d2) (1 - h1^2)
-#pragma unroll
-    for (int g = 0; g < 16; ++g) c[g] = 0.0f;
-#pragma unroll 8
-    for (int st = 0; st < kH / 2; ++st)
-      c = mfma(sW2[(2 * st + h) * kW2Ld + 32 * w + r], sD2[(2 * st + h) * kLd + r], c);
-#pragma unroll
-    for (int g = 0; g < 16; ++g)
-      sD1[(32 * w + acc_row(g, h)) * kLd + r] = c[g] * (1.0f - h1[g] * h1[g]);
-    // dW2 rows 32 w .. 32 w + 31
-#pragma unroll 4
-    for (int st = 0; st < kTile / 2; ++st) {
-      const float av = sD2[(32 * w + r) * kLd + 2 * st + h];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) accW2[t] = mfma(av, sH1[(32 * t + r) * kLd + 2 * st + h], accW2[t]);
-    }
-    __syncthreads();
-
-    // the sample sums of the small tensors, one thread per unit
-    if (tid < kH) {  // dW1 row and db1 of unit tid
-#pragma unroll 4
-      for (int s = 0; s < kTile; ++s) {
-        const float d = sD1[tid * kLd + s];
-        accS[8] += d;
-#pragma unroll
-        for (int o = 0; o < kMaxO; ++o) accS[o] = fmaf(d, sX[o * kTile + s], accS[o]);
-      }
-    } else {  // db2 and the head rows' column of unit tid - 128
-      const int u = tid - kH;
-#pragma unroll 4
-      for (int s = 0; s < kTile; ++s) {
-        accS[8] += sD2[u * kLd + s];
-        const float hv = sH2[u * kLd + s];
-#pragma unroll
-        for (int j = 0; j < kMaxA; ++j) accS[j] = fmaf(sDO[j * kTile + s], hv, accS[j]);
-      }
-    }
-    // every workgroup has at least one tile (the grid is no larger than the tile count),
-    // so the last tile's flush writes every entry of the slot at least once
-    if (++since == kFlushTiles || tile + nwg >= ntiles) flush();
-    __syncthreads();
-  }
-
-  // the float64 per-lane sums of wave 0's lower half, added in lane order
-  constexpr int kRedLd = 2 + 2 * kMaxA;
-  if (w == 0 && h == 0) {
-    double* p = sRed + r * kRedLd;
-    p[0] = lossS;
-    p[1] = entS;
-#pragma unroll
-    for (int j = 0; j < kMaxA; ++j) {
-      p[2 + j] = dbh[j];
-      p[2 + kMaxA + j] = dls[j];
-    }
-  }
-  // the count is exact in any order
-  double cnt = cntS;
-  if (w == 0) {
-#pragma unroll
-    for (int m = 1; m < 32; m <<= 1) cnt += __shfl_xor(cnt, m, 64);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double t[kRedLd];
-#pragma unroll
-    for (int i = 0; i < kRedLd; ++i) t[i] = 0.0;
-#pragma unroll 1
-    for (int s = 0; s < kTile; ++s)
-#pragma unroll
-      for (int i = 0; i < kRedLd; ++i) t[i] += sRed[s * kRedLd + i];
-#pragma unroll
-    for (int j = 0; j < kMaxA; ++j)
-      if (j < NH) slot[oBh + j] = t[2 + j];
-    if (pi) {
-#pragma unroll
-      for (int j = 0; j < kMaxA; ++j)
-        if (j < A) slot[oLs + j] = t[2 + kMaxA + j];
-      slot[P + 0] = t[0];
-      slot[P + 2] = t[1];
-      slot[P + 3] = cnt;
-    } else {
-      slot[P + 1] = t[0];
-    }
-  }
-}
+#define LZ_GRAD_PPO 0
+#define LZ_GRAD_KERNEL k_a2c_grad
+#include "lz_grad_body.inc"
+#undef LZ_GRAD_KERNEL
+#undef LZ_GRAD_PPO
 
 // out[i] = the slots' entries i added in slot order
 __global__ __launch_bounds__(256) void k_a2c_reduce(const double* __restrict__ part, int nwg,
@@ -452,14 +103,6 @@ __global__ __launch_bounds__(1024) void k_a2c_apply(ApplyArgs a) {
     a.stats[7] = a.lr;
   }
 }
-
-static int wgs_per_net(int64_t n, int cap) {
-  const int64_t tiles = (n + kTile - 1) / kTile;
-  const int64_t lim = cap > 0 ? cap : kDefaultWgs;
-  return (int)(tiles < lim ? tiles : lim);
-}
-
-static bool dims_ok(int O, int A) { return O >= 1 && O <= kMaxO && A >= 1 && A <= kMaxA; }
 
 }  // namespace a2c
 }  // namespace lz

@@ -1145,6 +1145,10 @@ def a2c_param_layout(obs_dim, act_dim):
     return out, o
 
 
+def _stream_ptr(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
 def a2c_grad(params, observations, actions, advantages, returns, obs_dim, act_dim, vf_coef=0.5,
              ent_coef=0.0, max_workgroups=0, workspace=None, out=None, hidden=HIDDEN):
     """lz_a2c_grad_f32 on the current stream: float64 device tensor [P + 4] of gradient sums
@@ -1178,8 +1182,7 @@ def a2c_grad(params, observations, actions, advantages, returns, obs_dim, act_di
     if out is None:
         out = torch.empty((P + 4,), dtype=torch.float64, device=dev)
     g.grad_sums = check_buffer(out, "grad_sums", torch.float64, P + 4, dev)
-    nat.check(nat.lib.lz_a2c_grad_f32(ctypes.byref(g), dev.index,
-                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    nat.check(nat.lib.lz_a2c_grad_f32(ctypes.byref(g), dev.index, _stream_ptr(dev)))
     return out
 
 
@@ -1202,12 +1205,99 @@ def a2c_apply(grad_sums, params, square_avg, lr, max_grad_norm=0.5, alpha=0.99, 
     if stats is None:
         stats = torch.empty((8,), dtype=torch.float64, device=dev)
     a.stats = check_buffer(stats, "stats", torch.float64, 8, dev)
-    nat.check(nat.lib.lz_a2c_apply_f32(ctypes.byref(a), dev.index,
-                                       ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    nat.check(nat.lib.lz_a2c_apply_f32(ctypes.byref(a), dev.index, _stream_ptr(dev)))
     return stats
 
 
-class FusedA2C:
+class _FusedLearner:
+    """What FusedA2C and FusedPPO share: the collectors they refuse, the policy as one flat
+    float32 device vector in a2c_param_layout's order, the schedules, and SB3's
+    OnPolicyAlgorithm.learn loop around the subclass's per-rollout step."""
+
+    def __init__(self, collector, state_dict, learning_rate, n_steps):
+        who = type(self).__name__
+        if is_attention_policy(state_dict) or is_attention_ln_policy(state_dict):
+            raise ValueError("%s updates the MlpPolicy; the attention policies' update is "
+                             "not implemented" % who)
+        if collector.precision in ("bf16", "i8x4"):
+            raise ValueError("%s needs a float32 collector (precision='fp32'), not %r"
+                             % (who, collector.precision))
+        if collector.frame_stack != 1:
+            raise ValueError("%s updates the MlpPolicy (frame_stack=1)" % who)
+        self.collector = collector
+        self.device = collector.device
+        self.O, self.A = collector.O, collector.A
+        self.layout, self.P = a2c_param_layout(self.O, self.A)
+        flat = []
+        for k, (_, shp) in self.layout.items():
+            if k not in state_dict:
+                raise KeyError("policy state_dict lacks %r" % k)
+            t = torch.as_tensor(_np(state_dict[k]))
+            if tuple(t.shape) != tuple(shp):
+                raise ValueError("%s has shape %s, expected %s (%s implements hidden=%d)"
+                                 % (k, tuple(t.shape), shp, who, HIDDEN))
+            flat.append(t.reshape(-1))
+        self.params = torch.cat(flat).to(self.device).contiguous()
+        self.learning_rate = learning_rate
+        self.n_steps = int(n_steps)
+        self.num_timesteps = 0
+        self.progress_remaining = 1.0
+        self._ws = None
+
+    def _now(self, v):
+        """A float, or a schedule of SB3's progress_remaining, as of now."""
+        return float(v(self.progress_remaining)) if callable(v) else float(v)
+
+    def _lr(self):
+        return self._now(self.learning_rate)
+
+    def _by_key(self, vec):
+        flat = vec.detach().cpu()
+        return {k: flat[o:o + int(np.prod(shp))].reshape(shp).clone()
+                for k, (o, shp) in self.layout.items()}
+
+    def state_dict(self):
+        """SB3 keys -> float32 CPU tensors (one device-to-host copy)."""
+        return self._by_key(self.params)
+
+    def _workspace(self, need):
+        """The gradient kernels' float64 workspace, grown to `need` entries."""
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty((max(need, 1),), dtype=torch.float64, device=self.device)
+        return self._ws
+
+    def _step(self, batch):
+        """The update on one rollout (FusedA2C.update, FusedPPO.train): returns its stats."""
+        raise NotImplementedError
+
+    def _world_size(self):
+        """The ranks whose rollouts count into num_timesteps."""
+        return 1
+
+    def learn(self, total_timesteps, callback=None):
+        """SB3 OnPolicyAlgorithm.learn: rollouts of n_steps x num_envs timesteps until
+        total_timesteps, progress_remaining = 1 - num_timesteps / total_timesteps updated
+        after each collect (what the schedules see in the update); gamma and gae_lambda are
+        the collector's.  callback(self, batch, stats) runs after every update.  Returns the
+        list of the updates' stats."""
+        total = int(total_timesteps)
+        col = self.collector
+        n = col.n * self._world_size()
+        out = []
+        start = self.num_timesteps
+        while self.num_timesteps - start < total:
+            batch = col.collect(self.n_steps)
+            self.num_timesteps += self.n_steps * n
+            self.progress_remaining = 1.0 - float(self.num_timesteps - start) / float(total)
+            col.compute_returns_and_advantage(batch)
+            stats = self._step(batch)
+            out.append(stats)
+            if callback is not None:
+                callback(self, batch, stats)
+        return out
+
+
+class FusedA2C(_FusedLearner):
     """SB3 A2C on a FusedRolloutCollector: ``learn`` is the loop collect(n_steps) ->
     compute_returns_and_advantage -> update, and ``update`` one A2C.train() -- the whole
     rollout as one batch, loss = -mean(adv log_prob) + vf_coef mse(returns, values) +
@@ -1228,55 +1318,17 @@ class FusedA2C:
                              "option; the reference leaves it off)")
         if not use_rms_prop:
             raise ValueError("FusedA2C: only RMSpropTFLike (use_rms_prop=True) is implemented")
-        if is_attention_policy(state_dict) or is_attention_ln_policy(state_dict):
-            raise ValueError("FusedA2C updates the MlpPolicy; the attention policies' update is "
-                             "not implemented")
-        if collector.precision in ("bf16", "i8x4"):
-            raise ValueError("FusedA2C needs a float32 collector (precision='fp32'), not %r"
-                             % collector.precision)
-        if collector.frame_stack != 1:
-            raise ValueError("FusedA2C updates the MlpPolicy (frame_stack=1)")
-        self.collector = collector
-        self.device = collector.device
-        self.O, self.A = collector.O, collector.A
-        self.layout, self.P = a2c_param_layout(self.O, self.A)
-        flat = []
-        for k, (_, shp) in self.layout.items():
-            if k not in state_dict:
-                raise KeyError("policy state_dict lacks %r" % k)
-            t = torch.as_tensor(_np(state_dict[k]))
-            if tuple(t.shape) != tuple(shp):
-                raise ValueError("%s has shape %s, expected %s (FusedA2C implements hidden=%d)"
-                                 % (k, tuple(t.shape), shp, HIDDEN))
-            flat.append(t.reshape(-1))
-        self.params = torch.cat(flat).to(self.device).contiguous()
+        super().__init__(collector, state_dict, learning_rate, n_steps)
         self.square_avg = torch.ones_like(self.params)  # RMSpropTFLike starts at ones
-        self.learning_rate = learning_rate
-        self.n_steps = int(n_steps)
         self.vf_coef, self.ent_coef = float(vf_coef), float(ent_coef)
         self.max_grad_norm, self.rms_prop_eps = float(max_grad_norm), float(rms_prop_eps)
         self.group = group
-        self.num_timesteps = 0
-        self.progress_remaining = 1.0
         self._sums = torch.empty((self.P + 4,), dtype=torch.float64, device=self.device)
-        self._ws = None
         collector.set_params(self.state_dict())
-
-    def _lr(self):
-        lr = self.learning_rate
-        return float(lr(self.progress_remaining)) if callable(lr) else float(lr)
-
-    def state_dict(self):
-        """SB3 keys -> float32 CPU tensors (one device-to-host copy)."""
-        flat = self.params.detach().cpu()
-        return {k: flat[o:o + int(np.prod(shp))].reshape(shp).clone()
-                for k, (o, shp) in self.layout.items()}
 
     def optimizer_state(self):
         """{"square_avg": {SB3 key: float32 CPU tensor}}: RMSpropTFLike's state."""
-        flat = self.square_avg.detach().cpu()
-        return {"square_avg": {k: flat[o:o + int(np.prod(shp))].reshape(shp).clone()
-                               for k, (o, shp) in self.layout.items()}}
+        return {"square_avg": self._by_key(self.square_avg)}
 
     def update(self, batch, lr=None):
         """One gradient step on the whole RolloutBatch (advantages / returns set by
@@ -1286,11 +1338,9 @@ class FusedA2C:
             raise ValueError("FusedA2C.update: compute_returns_and_advantage(batch) first")
         lr = self._lr() if lr is None else float(lr)
         B = int(batch.advantages.numel())
-        need = int(nat.lib.lz_a2c_workspace_bytes(B, self.O, self.A, 0)) // 8
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty((max(need, 1),), dtype=torch.float64, device=self.device)
+        ws = self._workspace(int(nat.lib.lz_a2c_workspace_bytes(B, self.O, self.A, 0)) // 8)
         a2c_grad(self.params, batch.observations, batch.actions, batch.advantages, batch.returns,
-                 self.O, self.A, self.vf_coef, self.ent_coef, workspace=self._ws, out=self._sums)
+                 self.O, self.A, self.vf_coef, self.ent_coef, workspace=ws, out=self._sums)
         if self.group is not None:
             dist.all_reduce(self._sums, group=self.group)
         stats = a2c_apply(self._sums, self.params, self.square_avg, lr, self.max_grad_norm, 0.99,
@@ -1298,36 +1348,17 @@ class FusedA2C:
         self.collector.set_params(self.state_dict())
         return dict(zip(nat.A2C_STATS, stats.cpu().tolist()))
 
-    def learn(self, total_timesteps, callback=None):
-        """SB3 OnPolicyAlgorithm.learn: rollouts of n_steps x num_envs timesteps until
-        total_timesteps, progress_remaining = 1 - num_timesteps / total_timesteps updated
-        after each collect (what the schedule sees in train()).  callback(self, batch, stats)
-        runs after every update.  Returns the list of the updates' stats."""
-        total = int(total_timesteps)
-        col = self.collector
-        n = col.n * (dist.get_world_size(self.group) if self.group is not None else 1)
-        out = []
-        start = self.num_timesteps
-        while self.num_timesteps - start < total:
-            batch = col.collect(self.n_steps)
-            self.num_timesteps += self.n_steps * n
-            self.progress_remaining = 1.0 - float(self.num_timesteps - start) / float(total)
-            col.compute_returns_and_advantage(batch)
-            stats = self.update(batch)
-            out.append(stats)
-            if callback is not None:
-                callback(self, batch, stats)
-        return out
+    def _step(self, batch):
+        return self.update(batch)
+
+    def _world_size(self):
+        return dist.get_world_size(self.group) if self.group is not None else 1
 
 
 # ------------------------------------------------------------------------------ PPO update
 # SB3 2.7.1 PPO.train() for the float32 MlpPolicy on the device (lz_ppo_adv_moments +
 # lz_ppo_grad_f32 + lz_adam_apply_f32 per minibatch): the update of code/train.py:97-129's,
 # code/lorenz_filter/train.py's and code/gym_run.py:83's learners.
-def _stream_ptr(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _check_indices(indices, n_rows, dev, who):
     """(pointer or None, M) of a minibatch's row list: int32, on the device, contiguous,
     at least one entry (its values are checked by the kernels, on the device)."""
@@ -1432,7 +1463,7 @@ def adam_apply(grad_sums, params, exp_avg, exp_avg_sq, ctrl, lr, max_grad_norm=0
     return stats
 
 
-class FusedPPO:
+class FusedPPO(_FusedLearner):
     """SB3 PPO on a FusedRolloutCollector: ``learn`` is the loop collect(n_steps) ->
     compute_returns_and_advantage -> train, and ``train`` one PPO.train(): n_epochs
     permutations of the rollout's rows cut into minibatches of batch_size, each one
@@ -1448,66 +1479,28 @@ class FusedPPO:
     def __init__(self, collector, state_dict, learning_rate=3e-4, n_steps=2048, batch_size=64,
                  n_epochs=10, clip_range=0.2, clip_range_vf=None, normalize_advantage=True,
                  ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, target_kl=None, generator=None):
-        if is_attention_policy(state_dict) or is_attention_ln_policy(state_dict):
-            raise ValueError("FusedPPO updates the MlpPolicy; the attention policies' update is "
-                             "not implemented")
-        if collector.precision in ("bf16", "i8x4"):
-            raise ValueError("FusedPPO needs a float32 collector (precision='fp32'), not %r"
-                             % collector.precision)
-        if collector.frame_stack != 1:
-            raise ValueError("FusedPPO updates the MlpPolicy (frame_stack=1)")
         if int(batch_size) < 1 or int(n_epochs) < 1 or int(n_steps) < 1:
             raise ValueError("FusedPPO: n_steps, batch_size and n_epochs must be >= 1")
         if normalize_advantage and int(batch_size) < 2:
             raise ValueError("FusedPPO: batch_size must be > 1 with normalize_advantage "
                              "(SB3 asserts it)")
-        self.collector = collector
-        self.device = collector.device
-        self.O, self.A = collector.O, collector.A
-        self.layout, self.P = a2c_param_layout(self.O, self.A)
-        flat = []
-        for k, (_, shp) in self.layout.items():
-            if k not in state_dict:
-                raise KeyError("policy state_dict lacks %r" % k)
-            t = torch.as_tensor(_np(state_dict[k]))
-            if tuple(t.shape) != tuple(shp):
-                raise ValueError("%s has shape %s, expected %s (FusedPPO implements hidden=%d)"
-                                 % (k, tuple(t.shape), shp, HIDDEN))
-            flat.append(t.reshape(-1))
+        super().__init__(collector, state_dict, learning_rate, n_steps)
         dev = self.device
-        self.params = torch.cat(flat).to(dev).contiguous()
         self.exp_avg = torch.zeros_like(self.params)
         self.exp_avg_sq = torch.zeros_like(self.params)
         self.ctrl = torch.zeros((2,), dtype=torch.int64, device=dev)  # Adam's step, stopped
-        self.learning_rate, self.clip_range, self.clip_range_vf = learning_rate, clip_range, clip_range_vf
-        self.n_steps, self.batch_size, self.n_epochs = int(n_steps), int(batch_size), int(n_epochs)
+        self.clip_range, self.clip_range_vf = clip_range, clip_range_vf
+        self.batch_size, self.n_epochs = int(batch_size), int(n_epochs)
         self.normalize_advantage = bool(normalize_advantage)
         self.vf_coef, self.ent_coef = float(vf_coef), float(ent_coef)
         self.max_grad_norm = float(max_grad_norm)
         self.target_kl = None if target_kl is None else float(target_kl)
         self.generator = generator
-        self.num_timesteps = 0
         self.n_updates = 0
-        self.progress_remaining = 1.0
         self._sums = torch.empty((self.P + 6,), dtype=torch.float64, device=dev)
         self._mom = torch.empty((2,), dtype=torch.float64, device=dev)
-        self._ws = self._perm = self._stats = None
+        self._perm = self._stats = None
         collector.set_params(self.state_dict())
-
-    def _now(self, v):
-        return float(v(self.progress_remaining)) if callable(v) else float(v)
-
-    def _lr(self):
-        return self._now(self.learning_rate)
-
-    def state_dict(self):
-        """SB3 keys -> float32 CPU tensors (one device-to-host copy)."""
-        return self._by_key(self.params)
-
-    def _by_key(self, vec):
-        flat = vec.detach().cpu()
-        return {k: flat[o:o + int(np.prod(shp))].reshape(shp).clone()
-                for k, (o, shp) in self.layout.items()}
 
     def optimizer_state(self):
         """{"exp_avg": {SB3 key: float32 CPU tensor}, "exp_avg_sq": {...}, "step": int}:
@@ -1535,9 +1528,7 @@ class FusedPPO:
         dev = self.device
         B = int(batch.advantages.numel())
         cuts = self.minibatches(B)
-        need = int(nat.lib.lz_ppo_workspace_bytes(min(self.batch_size, B), self.O, self.A, 0)) // 8
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty((max(need, 1),), dtype=torch.float64, device=dev)
+        self._workspace(int(nat.lib.lz_ppo_workspace_bytes(min(self.batch_size, B), self.O, self.A, 0)) // 8)
         if self._perm is None or self._perm.numel() != B:
             self._perm = torch.empty((B,), dtype=torch.int32, device=dev)
         rows = self.n_epochs * len(cuts)
@@ -1577,23 +1568,5 @@ class FusedPPO:
                    self.max_grad_norm, (0.9, 0.999), 1e-5, self.vf_coef, self.ent_coef, self.target_kl,
                    stats=stats_row)
 
-    def learn(self, total_timesteps, callback=None):
-        """SB3 OnPolicyAlgorithm.learn: rollouts of n_steps x num_envs timesteps until
-        total_timesteps, progress_remaining = 1 - num_timesteps / total_timesteps updated
-        after each collect (what the schedules see in train()); gamma and gae_lambda are
-        the collector's.  callback(self, batch, stats) runs after every train().  Returns the
-        list of the updates' stats."""
-        total = int(total_timesteps)
-        col = self.collector
-        out = []
-        start = self.num_timesteps
-        while self.num_timesteps - start < total:
-            batch = col.collect(self.n_steps)
-            self.num_timesteps += self.n_steps * col.n
-            self.progress_remaining = 1.0 - float(self.num_timesteps - start) / float(total)
-            col.compute_returns_and_advantage(batch)
-            stats = self.train(batch)
-            out.append(stats)
-            if callback is not None:
-                callback(self, batch, stats)
-        return out
+    def _step(self, batch):
+        return self.train(batch)
