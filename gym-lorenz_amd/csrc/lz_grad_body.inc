@@ -1,7 +1,8 @@
 // The gradient kernel of the float32 MlpPolicy, from __global__ to its closing brace.
-// lz_a2c.hip (inside lz::a2c) and lz_ppo.hip (inside lz::ppo) each include this file once,
-// after their GradArgs and after defining
+// lz_a2c.hip (inside lz::a2c) and lz_ppo.hip (inside lz::ppo) each include this file once
+// per hidden size, after their GradArgs and after defining
 //   LZ_GRAD_PPO     0: k_a2c_grad, 1: k_ppo_grad
+//   LZ_GRAD_H       hidden units: 128, or 64 (the _h64 kernels)
 //   LZ_GRAD_KERNEL  the kernel's name
 //   kTail           doubles after the P gradient sums in a workgroup's slot
 //   kLaneSums       float64 per-lane loss sums that go through the lane-order reduction
@@ -35,18 +36,34 @@
 // slot of the workspace, no atomics) every kFlushTiles tiles, so no float32 chain is longer
 // than 2048 samples whatever the batch; the reduce kernel adds the slots in slot order.  Two
 // launches on the same inputs give the same bits.
-#if !defined(LZ_GRAD_PPO) || !defined(LZ_GRAD_KERNEL)
-#error "lz_grad_body.inc: define LZ_GRAD_PPO to 0 or 1 and LZ_GRAD_KERNEL to the kernel's name"
+//
+// The hidden size is the including file's too: LZ_GRAD_H is 128 (k_a2c_grad, k_ppo_grad: the
+// figures above) or 64 (k_a2c_grad_h64, k_ppo_grad_h64: SB3's default MlpPolicy).  Everything
+// that depends on it is a constant below: kWaves = kH / 32 waves, kThreads = 2 kH threads (one
+// per unit for each of the two per-unit sample sums), W2 row stride kH + 1, kWaves accumulator
+// tiles of dW2 and kWaves head partials per sample.  The 64-unit form computes what the
+// 128-unit form computes on the zero-padded net: the padded units add exact zeros to every
+// chain, and the tiles, flushes and slots are the same.
+#if !defined(LZ_GRAD_PPO) || !defined(LZ_GRAD_KERNEL) || !defined(LZ_GRAD_H)
+#error "lz_grad_body.inc: define LZ_GRAD_PPO to 0 or 1, LZ_GRAD_KERNEL to the kernel's name, LZ_GRAD_H to 128 or 64"
+#endif
+#if LZ_GRAD_H != 128 && LZ_GRAD_H != 64
+#error "lz_grad_body.inc: LZ_GRAD_H must be 128 or 64"
 #endif
 
-__global__ __launch_bounds__(256) void LZ_GRAD_KERNEL(GradArgs a) {
+__global__ __launch_bounds__(2 * LZ_GRAD_H) void LZ_GRAD_KERNEL(GradArgs a) {
+  constexpr int kH = LZ_GRAD_H;         // hidden units (hides grad::kH)
+  constexpr int kLogH = kH == 128 ? 7 : 6;
+  constexpr int kW2Ld = kH + 1;         // row stride of the W2 image
+  constexpr int kWaves = kH / 32;       // wave w owns units 32 w .. 32 w + 31
+  constexpr int kThreads = 2 * kH;      // = 64 kWaves
   __shared__ float sW2[kH * kW2Ld];
   __shared__ float sW1[kH * kMaxO];
   __shared__ float sB1[kH], sB2[kH];
   __shared__ float sWh[kMaxA * kH];
   __shared__ float sX[kMaxO * kTile];
   __shared__ float sH1[kH * kLd], sH2[kH * kLd], sD2[kH * kLd], sD1[kH * kLd];
-  __shared__ float sHP[4 * kMaxA * kTile];
+  __shared__ float sHP[kWaves * kMaxA * kTile];
   __shared__ float sDO[kMaxA * kTile];
   constexpr int kRedLd = kLaneSums + 2 * kMaxA;
   __shared__ double sRed[kTile * kRedLd];
@@ -60,7 +77,7 @@ __global__ __launch_bounds__(256) void LZ_GRAD_KERNEL(GradArgs a) {
   const bool pi = (blockIdx.x & 1u) == 0;
   const int wg = (int)(blockIdx.x >> 1), nwg = (int)(gridDim.x >> 1);
   const int O = a.O, A = a.A, NH = pi ? A : 1;
-  const Layout L = layout(O, A);
+  const Layout L = layout(O, A, kH);
   // (selected, not indexed: a runtime index would put the table in scratch)
   const int64_t oW1 = pi ? L.off[0] : L.off[4], oB1 = pi ? L.off[1] : L.off[5];
   const int64_t oW2 = pi ? L.off[2] : L.off[6], oB2 = pi ? L.off[3] : L.off[7];
@@ -74,17 +91,17 @@ __global__ __launch_bounds__(256) void LZ_GRAD_KERNEL(GradArgs a) {
   const float* gBh = a.params + oBh;
   const float* gLs = a.params + oLs;
 
-  for (int e = tid; e < kH * kH; e += 256) sW2[(e >> 7) * kW2Ld + (e & 127)] = gW2[e];
-  for (int e = tid; e < kH * kMaxO; e += 256) {
+  for (int e = tid; e < kH * kH; e += kThreads) sW2[(e >> kLogH) * kW2Ld + (e & (kH - 1))] = gW2[e];
+  for (int e = tid; e < kH * kMaxO; e += kThreads) {
     const int u = e >> 3, k = e & 7;
     sW1[e] = k < O ? gW1[u * O + k] : 0.0f;
   }
-  for (int e = tid; e < kH; e += 256) {
+  for (int e = tid; e < kH; e += kThreads) {
     sB1[e] = gB1[e];
     sB2[e] = gB2[e];
   }
-  for (int e = tid; e < kMaxA * kH; e += 256) sWh[e] = e < NH * kH ? gWh[e] : 0.0f;
-  for (int e = tid; e < kMaxA * kTile; e += 256) sDO[e] = 0.0f;
+  for (int e = tid; e < kMaxA * kH; e += kThreads) sWh[e] = e < NH * kH ? gWh[e] : 0.0f;
+  for (int e = tid; e < kMaxA * kTile; e += kThreads) sDO[e] = 0.0f;
   float bh[kMaxA], ls[kMaxA], inv_var[kMaxA];
 #pragma unroll
   for (int j = 0; j < kMaxA; ++j) {
@@ -101,9 +118,9 @@ __global__ __launch_bounds__(256) void LZ_GRAD_KERNEL(GradArgs a) {
 #endif
   __syncthreads();
 
-  v16 accW2[4];
+  v16 accW2[kWaves];
 #pragma unroll
-  for (int t = 0; t < 4; ++t)
+  for (int t = 0; t < kWaves; ++t)
 #pragma unroll
     for (int g = 0; g < 16; ++g) accW2[t][g] = 0.0f;
   float accS[9];
@@ -125,7 +142,7 @@ __global__ __launch_bounds__(256) void LZ_GRAD_KERNEL(GradArgs a) {
   auto flush = [&]() __attribute__((always_inline)) {
     double* pW2 = slot + oW2;
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
+    for (int t = 0; t < kWaves; ++t)
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
         put(pW2 + (32 * w + acc_row(g, h)) * kH + 32 * t + r, accW2[t][g], first);
@@ -162,13 +179,19 @@ __global__ __launch_bounds__(256) void LZ_GRAD_KERNEL(GradArgs a) {
     if (a.idx && si < a.n) row = (int64_t)a.idx[si];
     const bool valid = si < a.n && row >= 0 && row < a.n_rows;
     const bool bad = si < a.n && !valid;
-    {  // x as [k][sample]; rows k >= O and samples that are not read are 0
-      const int k = tid >> 5;
+    // x as [k][sample]; rows k >= O and samples that are not read are 0 (kThreads / 32 rows
+    // a pass: one pass with 256 threads, two with 128)
+#pragma unroll
+    for (int k0 = 0; k0 < kMaxO; k0 += kThreads / 32) {
+      const int k = k0 + (tid >> 5);
       sX[k * kTile + r] = (k < O && valid) ? a.obs[row * O + k] : 0.0f;
     }
 #else
-    {  // x as [k][sample]; rows k >= O and samples past the end are 0
-      const int k = tid >> 5, s = tid & 31;
+    // x as [k][sample]; rows k >= O and samples past the end are 0 (kThreads / 32 rows a
+    // pass: one pass with 256 threads, two with 128)
+#pragma unroll
+    for (int k0 = 0; k0 < kMaxO; k0 += kThreads / 32) {
+      const int k = k0 + (tid >> 5), s = tid & 31;
       const int64_t i = base + s;
       sX[k * kTile + s] = (k < O && i < a.n) ? a.obs[i * O + k] : 0.0f;
     }
@@ -222,9 +245,12 @@ __global__ __launch_bounds__(256) void LZ_GRAD_KERNEL(GradArgs a) {
 #pragma unroll
       for (int j = 0; j < kMaxA; ++j) {
         out[j] = 0.0f;
-        if (j < NH)
-          out[j] = (((sHP[(0 * kMaxA + j) * kTile + r] + sHP[(1 * kMaxA + j) * kTile + r]) +
-                     sHP[(2 * kMaxA + j) * kTile + r]) + sHP[(3 * kMaxA + j) * kTile + r]) + bh[j];
+        if (j < NH) {  // the waves' partials in wave order, then the bias
+          float p = sHP[(0 * kMaxA + j) * kTile + r];
+#pragma unroll
+          for (int ww = 1; ww < kWaves; ++ww) p += sHP[(ww * kMaxA + j) * kTile + r];
+          out[j] = p + bh[j];
+        }
         dout[j] = 0.0f;
       }
       // wave 0's lower half keeps the float64 sums (PPO tells `valid` from `bad` per sum)
@@ -364,7 +390,7 @@ __global__ __launch_bounds__(256) void LZ_GRAD_KERNEL(GradArgs a) {
     for (int st = 0; st < kTile / 2; ++st) {
       const float av = sD2[(32 * w + r) * kLd + 2 * st + h];
 #pragma unroll
-      for (int t = 0; t < 4; ++t) accW2[t] = mfma(av, sH1[(32 * t + r) * kLd + 2 * st + h], accW2[t]);
+      for (int t = 0; t < kWaves; ++t) accW2[t] = mfma(av, sH1[(32 * t + r) * kLd + 2 * st + h], accW2[t]);
     }
     __syncthreads();
 
@@ -377,7 +403,7 @@ __global__ __launch_bounds__(256) void LZ_GRAD_KERNEL(GradArgs a) {
 #pragma unroll
         for (int o = 0; o < kMaxO; ++o) accS[o] = fmaf(d, sX[o * kTile + s], accS[o]);
       }
-    } else {  // db2 and the head rows' column of unit tid - 128
+    } else {  // db2 and the head rows' column of unit tid - kH
       const int u = tid - kH;
 #pragma unroll 4
       for (int s = 0; s < kTile; ++s) {

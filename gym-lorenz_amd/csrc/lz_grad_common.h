@@ -13,26 +13,26 @@ namespace grad {
 
 typedef float v16 __attribute__((ext_vector_type(16)));
 
-constexpr int kH = 128;          // hidden units (LZ_POLICY_HIDDEN)
+constexpr int kH = 128;          // hidden units of the first form (LZ_POLICY_HIDDEN)
+constexpr int kH64 = 64;         // hidden units of the _h64 form (SB3's default MlpPolicy)
 constexpr int kTile = 32;        // samples per workgroup tile
 constexpr int kLd = 33;          // row stride of the [unit][sample] images
-constexpr int kW2Ld = 129;       // row stride of the W2 image
 constexpr int kMaxO = 8, kMaxA = 4;
 constexpr int kFlushTiles = 64;  // float32 chains end after 64 * 32 samples
 constexpr int kDefaultWgs = 128; // workgroups per net when the caller sets no cap
 constexpr int kMaxWgs = 4096;
 
 // offsets of the 13 tensors (gym_lorenz.policy.KEYS order, nn.Linear layout) in the flat
-// parameter vector, and its length (lz_a2c_param_count)
+// parameter vector of a net with H hidden units, and its length (lz_a2c_param_count_hidden)
 struct Layout {
   int64_t off[13];
   int64_t P;
 };
 
-__host__ __device__ inline Layout layout(int O, int A) {
+__host__ __device__ inline Layout layout(int O, int A, int H = kH) {
   Layout L;
-  const int64_t n[13] = {(int64_t)kH * O, kH, (int64_t)kH * kH, kH, (int64_t)kH * O, kH,
-                         (int64_t)kH * kH, kH, (int64_t)A * kH, A, kH, 1, A};
+  const int64_t n[13] = {(int64_t)H * O, H, (int64_t)H * H, H, (int64_t)H * O, H,
+                         (int64_t)H * H, H, (int64_t)A * H, A, H, 1, A};
   int64_t o = 0;
   for (int i = 0; i < 13; ++i) {
     L.off[i] = o;
@@ -59,6 +59,9 @@ inline int wgs_per_net(int64_t n, int cap) {
 }
 
 inline bool dims_ok(int O, int A) { return O >= 1 && O <= kMaxO && A >= 1 && A <= kMaxA; }
+
+// the hidden sizes a gradient kernel is built for
+inline bool hidden_ok(int H) { return H == kH || H == kH64; }
 
 }  // namespace grad
 }  // namespace lz

@@ -36,10 +36,17 @@
 //   vf head phase   d_out = -2 vf_coef (ret - v_pred), 0 where |v - old_v| > clip_range_vf
 //   two more float64 per-lane sums: [|ratio - 1| > clip] and (ratio - 1) - log_ratio
 //   the launch returns at entry while ctrl[1] (the target_kl stop) is set
+//
+// k_ppo_grad_h64 is the same text with LZ_GRAD_H 64, the obs -> 64 -> 64 net of SB3's default
+// MlpPolicy: what code/train.py:106-118 and code/lorenz_filter/train.py:117-129 train (both
+// build a policy_kwargs dict and never pass it on) and what the reference's shipped PPO
+// policies hold (hr_sync_agent.zip: (64, 6) / (64, 64) / (1, 64));
+// lz_ppo_grad_hidden_f32 launches either form.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 
 #include "lz_grad_common.h"
 #include "lz_internal.h"
@@ -72,9 +79,17 @@ struct GradArgs {
 };
 
 #define LZ_GRAD_PPO 1
+#define LZ_GRAD_H 128
 #define LZ_GRAD_KERNEL k_ppo_grad
 #include "lz_grad_body.inc"
 #undef LZ_GRAD_KERNEL
+#undef LZ_GRAD_H
+// the same text for SB3's default 64 x 64 net: 2 waves, 128 threads (lz_ppo_grad_hidden_f32)
+#define LZ_GRAD_H 64
+#define LZ_GRAD_KERNEL k_ppo_grad_h64
+#include "lz_grad_body.inc"
+#undef LZ_GRAD_KERNEL
+#undef LZ_GRAD_H
 #undef LZ_GRAD_PPO
 
 // out[i] = the slots' entries i added in slot order (nothing after the stop, as k_ppo_grad)
@@ -234,6 +249,16 @@ extern "C" int64_t lz_ppo_workspace_bytes(int64_t n_samples, int32_t obs_dim, in
   return (int64_t)wgs_per_net(n_samples, max_workgroups) * (P + kTail) * (int64_t)sizeof(double);
 }
 
+extern "C" int64_t lz_ppo_workspace_bytes_hidden(int64_t n_samples, int32_t obs_dim, int32_t act_dim,
+                                                 int32_t hidden, int32_t max_workgroups) {
+  using namespace lz::ppo;
+  if (!dims_ok(obs_dim, act_dim) || !hidden_ok(hidden) || n_samples < 1 || max_workgroups < 0 ||
+      max_workgroups > kMaxWgs)
+    return -1;
+  const int64_t P = layout(obs_dim, act_dim, hidden).P;
+  return (int64_t)wgs_per_net(n_samples, max_workgroups) * (P + kTail) * (int64_t)sizeof(double);
+}
+
 extern "C" lz_status lz_ppo_adv_moments(const float* advantages, const int32_t* indices,
                                         int64_t n_samples, int64_t n_rows, void* workspace,
                                         double* out, int32_t device, void* stream) {
@@ -252,35 +277,48 @@ extern "C" lz_status lz_ppo_adv_moments(const float* advantages, const int32_t* 
   return LZ_OK;
 }
 
-extern "C" lz_status lz_ppo_grad_f32(const lz_ppo_grad_args* g, int32_t device, void* stream) {
+namespace {
+
+lz_status fail(lz_status s, const char* who, const char* what) {
+  char m[160];
+  snprintf(m, sizeof m, "%s: %s", who, what);
+  return lz::set_error(s, m);
+}
+
+// lz_ppo_grad_f32 (any_hidden false: 128 units only) and lz_ppo_grad_hidden_f32: the same
+// refusals in the same order, then the launch of the form built for g->hidden
+lz_status grad_entry(const lz_ppo_grad_args* g, int32_t device, void* stream, const char* who,
+                     bool any_hidden) {
   using namespace lz::ppo;
-  if (!g) return lz::set_error(LZ_ERR_INVALID, "lz_ppo_grad_f32: NULL args");
+  if (!g) return fail(LZ_ERR_INVALID, who, "NULL args");
   if (!g->params || !g->observations || !g->actions || !g->advantages || !g->returns ||
       !g->old_log_prob || !g->workspace || !g->grad_sums)
-    return lz::set_error(LZ_ERR_INVALID, "lz_ppo_grad_f32: NULL buffer");
+    return fail(LZ_ERR_INVALID, who, "NULL buffer");
   if (g->clip_range_vf > 0.0 && !g->old_values)
-    return lz::set_error(LZ_ERR_INVALID, "lz_ppo_grad_f32: NULL old_values with clip_range_vf > 0");
+    return fail(LZ_ERR_INVALID, who, "NULL old_values with clip_range_vf > 0");
   if (!dims_ok(g->obs_dim, g->act_dim))
-    return lz::set_error(LZ_ERR_INVALID, "lz_ppo_grad_f32: obs_dim must be 1..8 and act_dim 1..4");
-  if (g->n_samples < 1) return lz::set_error(LZ_ERR_INVALID, "lz_ppo_grad_f32: n_samples < 1");
-  if (g->n_rows < 1) return lz::set_error(LZ_ERR_INVALID, "lz_ppo_grad_f32: n_rows < 1");
+    return fail(LZ_ERR_INVALID, who, "obs_dim must be 1..8 and act_dim 1..4");
+  if (g->n_samples < 1) return fail(LZ_ERR_INVALID, who, "n_samples < 1");
+  if (g->n_rows < 1) return fail(LZ_ERR_INVALID, who, "n_rows < 1");
   if (!g->indices && g->n_samples > g->n_rows)
-    return lz::set_error(LZ_ERR_INVALID, "lz_ppo_grad_f32: n_samples > n_rows without indices");
+    return fail(LZ_ERR_INVALID, who, "n_samples > n_rows without indices");
   if (!(g->clip_range >= 0.0) || std::isinf(g->clip_range))
-    return lz::set_error(LZ_ERR_INVALID, "lz_ppo_grad_f32: clip_range must be finite and >= 0");
+    return fail(LZ_ERR_INVALID, who, "clip_range must be finite and >= 0");
   if (g->clip_range_vf != g->clip_range_vf || std::isinf(g->clip_range_vf))
-    return lz::set_error(LZ_ERR_INVALID, "lz_ppo_grad_f32: clip_range_vf must be finite");
+    return fail(LZ_ERR_INVALID, who, "clip_range_vf must be finite");
   if (g->max_workgroups < 0 || g->max_workgroups > kMaxWgs)
-    return lz::set_error(LZ_ERR_INVALID, "lz_ppo_grad_f32: max_workgroups must be 0..4096");
-  if (g->hidden != kH)
-    return lz::set_error(LZ_ERR_UNSUPPORTED, "lz_ppo_grad_f32: hidden must be 128");
-  const int64_t need = lz_ppo_workspace_bytes(g->n_samples, g->obs_dim, g->act_dim, g->max_workgroups);
+    return fail(LZ_ERR_INVALID, who, "max_workgroups must be 0..4096");
+  if (any_hidden ? !hidden_ok(g->hidden) : g->hidden != kH)
+    return fail(LZ_ERR_UNSUPPORTED, who, any_hidden ? "hidden must be 64 or 128" : "hidden must be 128");
+  const int64_t need = lz_ppo_workspace_bytes_hidden(g->n_samples, g->obs_dim, g->act_dim, g->hidden,
+                                                     g->max_workgroups);
   if (g->workspace_bytes < need)
-    return lz::set_error(LZ_ERR_INVALID, "lz_ppo_grad_f32: workspace smaller than lz_ppo_workspace_bytes");
+    return fail(LZ_ERR_INVALID, who, any_hidden ? "workspace smaller than lz_ppo_workspace_bytes_hidden"
+                                                : "workspace smaller than lz_ppo_workspace_bytes");
   if (hipSetDevice(device) != hipSuccess) return lz::set_error(LZ_ERR_HIP, "hipSetDevice failed");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nwg = wgs_per_net(g->n_samples, g->max_workgroups);
-  const int64_t len = layout(g->obs_dim, g->act_dim).P + kTail;
+  const int64_t len = layout(g->obs_dim, g->act_dim, g->hidden).P + kTail;
   GradArgs a;
   a.params = g->params;
   a.obs = g->observations;
@@ -304,12 +342,25 @@ extern "C" lz_status lz_ppo_grad_f32(const lz_ppo_grad_args* g, int32_t device, 
   a.clip_hi = (float)(1.0 + g->clip_range);
   a.clip_vf = (float)g->clip_range_vf;
   a.part = static_cast<double*>(g->workspace);
-  hipLaunchKernelGGL(k_ppo_grad, dim3(2u * (unsigned)nwg), dim3(256), 0, s, a);
+  if (g->hidden == kH64)
+    hipLaunchKernelGGL(k_ppo_grad_h64, dim3(2u * (unsigned)nwg), dim3(2 * kH64), 0, s, a);
+  else
+    hipLaunchKernelGGL(k_ppo_grad, dim3(2u * (unsigned)nwg), dim3(2 * kH), 0, s, a);
   hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s,
                      static_cast<const double*>(g->workspace), nwg, len, g->ctrl, g->grad_sums);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return lz::set_error(LZ_ERR_HIP, hipGetErrorString(e));
   return LZ_OK;
+}
+
+}  // namespace
+
+extern "C" lz_status lz_ppo_grad_f32(const lz_ppo_grad_args* g, int32_t device, void* stream) {
+  return grad_entry(g, device, stream, "lz_ppo_grad_f32", false);
+}
+
+extern "C" lz_status lz_ppo_grad_hidden_f32(const lz_ppo_grad_args* g, int32_t device, void* stream) {
+  return grad_entry(g, device, stream, "lz_ppo_grad_hidden_f32", true);
 }
 
 extern "C" lz_status lz_adam_apply_f32(const lz_adam_apply_args* p, int32_t device, void* stream) {

@@ -396,6 +396,13 @@ _SIGS = {
                                           ctypes.c_int32, VP]),
     "lz_ppo_grad_f32": (ctypes.c_int, [ctypes.POINTER(LzPpoGradArgs), ctypes.c_int32, VP]),
     "lz_adam_apply_f32": (ctypes.c_int, [ctypes.POINTER(LzAdamApplyArgs), ctypes.c_int32, VP]),
+    "lz_a2c_param_count_hidden": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "lz_a2c_workspace_bytes_hidden": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                       ctypes.c_int32, ctypes.c_int32]),
+    "lz_a2c_grad_hidden_f32": (ctypes.c_int, [ctypes.POINTER(LzA2cGradArgs), ctypes.c_int32, VP]),
+    "lz_ppo_workspace_bytes_hidden": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                       ctypes.c_int32, ctypes.c_int32]),
+    "lz_ppo_grad_hidden_f32": (ctypes.c_int, [ctypes.POINTER(LzPpoGradArgs), ctypes.c_int32, VP]),
     "lz_episode_starts": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, VP, VP, VP, VP,
                                          ctypes.c_int32, VP]),
     "lz_frame_stack": (ctypes.c_int, [VP, VP, VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,

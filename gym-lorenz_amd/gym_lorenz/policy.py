@@ -1129,17 +1129,21 @@ def linear_schedule(initial_value):
     return schedule
 
 
-def a2c_param_shapes(obs_dim, act_dim):
+LEARNER_HIDDEN = (64, HIDDEN)  # the hidden sizes the gradient kernels are built for
+
+
+def a2c_param_shapes(obs_dim, act_dim, hidden=HIDDEN):
     """The 13 tensors' shapes in KEYS order (nn.Linear layout)."""
-    H = HIDDEN
+    H = int(hidden)
     return [(H, obs_dim), (H,), (H, H), (H,)] * 2 + [(act_dim, H), (act_dim,), (1, H), (1,),
                                                       (act_dim,)]
 
 
-def a2c_param_layout(obs_dim, act_dim):
-    """{key: (offset, shape)} of lz_a2c_grad_f32's flat parameter vector, and its length."""
+def a2c_param_layout(obs_dim, act_dim, hidden=HIDDEN):
+    """{key: (offset, shape)} of lz_a2c_grad_f32's (lz_a2c_grad_hidden_f32's) flat parameter
+    vector, and its length."""
     out, o = {}, 0
-    for k, shp in zip(KEYS, a2c_param_shapes(obs_dim, act_dim)):
+    for k, shp in zip(KEYS, a2c_param_shapes(obs_dim, act_dim, hidden)):
         out[k] = (o, shp)
         o += int(np.prod(shp))
     return out, o
@@ -1149,18 +1153,52 @@ def _stream_ptr(dev):
     return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
+def net_arch_hidden(net_arch, who="net_arch"):
+    """SB3's policy_kwargs["net_arch"] -> the hidden size of a learner: H, [H, H] or
+    dict(pi=[H, H], vf=[H, H]) with H in LEARNER_HIDDEN; anything else is a ValueError."""
+    arch = net_arch
+    if isinstance(arch, dict):
+        if set(arch) != {"pi", "vf"} or list(arch["pi"]) != list(arch["vf"]):
+            raise ValueError("%s: net_arch must have equal pi and vf lists, not %r" % (who, net_arch))
+        arch = list(arch["pi"])
+    if isinstance(arch, (list, tuple)):
+        if len(arch) != 2 or arch[0] != arch[1]:
+            raise ValueError("%s: net_arch must be two equal layers, not %r" % (who, net_arch))
+        arch = arch[0]
+    if isinstance(arch, bool) or not isinstance(arch, (int, np.integer)) or int(arch) not in LEARNER_HIDDEN:
+        raise ValueError("%s: net_arch %r is not implemented (hidden sizes %s)"
+                         % (who, net_arch, " / ".join(str(h) for h in LEARNER_HIDDEN)))
+    return int(arch)
+
+
+def _grad_fns(kind, hidden, O, A, who):
+    """(P, workspace_bytes(n, max_workgroups), grad entry point) for a hidden size: the
+    first entry points at HIDDEN, the _hidden ones (lz_a2c_grad_hidden_f32, ...) otherwise."""
+    H = int(hidden)
+    if nat.lib.lz_a2c_param_count(O, A) < 0:
+        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "%s: obs_dim must be 1..8, act_dim 1..4" % who)
+    if H == HIDDEN:
+        P = int(nat.lib.lz_a2c_param_count(O, A))
+        ws = getattr(nat.lib, "lz_%s_workspace_bytes" % kind)
+        return P, (lambda n, cap: int(ws(n, O, A, cap))), getattr(nat.lib, "lz_%s_grad_f32" % kind)
+    P = int(nat.lib.lz_a2c_param_count_hidden(O, A, H))
+    if P < 0:
+        raise nat.LorenzEnvError(nat.LZ_ERR_UNSUPPORTED, "%s: hidden must be 64 or 128" % who)
+    ws = getattr(nat.lib, "lz_%s_workspace_bytes_hidden" % kind)
+    return P, (lambda n, cap: int(ws(n, O, A, H, cap))), getattr(nat.lib, "lz_%s_grad_hidden_f32" % kind)
+
+
 def a2c_grad(params, observations, actions, advantages, returns, obs_dim, act_dim, vf_coef=0.5,
              ent_coef=0.0, max_workgroups=0, workspace=None, out=None, hidden=HIDDEN):
-    """lz_a2c_grad_f32 on the current stream: float64 device tensor [P + 4] of gradient sums
-    over the samples, then sum(-adv log_prob), sum((ret - v)^2), sum(-entropy), the count.
-    Every buffer is checked (core.check_buffer) before the launch."""
+    """lz_a2c_grad_f32 (hidden=64: lz_a2c_grad_hidden_f32) on the current stream: float64
+    device tensor [P + 4] of gradient sums over the samples, then sum(-adv log_prob),
+    sum((ret - v)^2), sum(-entropy), the count.  Every buffer is checked (core.check_buffer)
+    before the launch."""
     dev = params.device
     O, A = int(obs_dim), int(act_dim)
     if dev.type != "cuda":
         raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "a2c_grad: params must be a device tensor")
-    P = int(nat.lib.lz_a2c_param_count(O, A))
-    if P < 0:
-        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "a2c_grad: obs_dim must be 1..8, act_dim 1..4")
+    P, ws_bytes, grad_fn = _grad_fns("a2c", hidden, O, A, "a2c_grad")
     B = int(advantages.numel())
     f32 = torch.float32
     g = nat.LzA2cGradArgs()
@@ -1172,7 +1210,7 @@ def a2c_grad(params, observations, actions, advantages, returns, obs_dim, act_di
     g.n_samples, g.obs_dim, g.act_dim, g.hidden = B, O, A, int(hidden)
     g.max_workgroups = int(max_workgroups)
     g.vf_coef, g.ent_coef = float(vf_coef), float(ent_coef)
-    need = int(nat.lib.lz_a2c_workspace_bytes(B, O, A, int(max_workgroups)))
+    need = ws_bytes(B, int(max_workgroups))
     if need < 0:
         raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "a2c_grad: empty batch or bad max_workgroups")
     if workspace is None:
@@ -1182,7 +1220,7 @@ def a2c_grad(params, observations, actions, advantages, returns, obs_dim, act_di
     if out is None:
         out = torch.empty((P + 4,), dtype=torch.float64, device=dev)
     g.grad_sums = check_buffer(out, "grad_sums", torch.float64, P + 4, dev)
-    nat.check(nat.lib.lz_a2c_grad_f32(ctypes.byref(g), dev.index, _stream_ptr(dev)))
+    nat.check(grad_fn(ctypes.byref(g), dev.index, _stream_ptr(dev)))
     return out
 
 
@@ -1214,8 +1252,10 @@ class _FusedLearner:
     float32 device vector in a2c_param_layout's order, the schedules, and SB3's
     OnPolicyAlgorithm.learn loop around the subclass's per-rollout step."""
 
-    def __init__(self, collector, state_dict, learning_rate, n_steps):
+    def __init__(self, collector, state_dict, learning_rate, n_steps, net_arch=None):
         who = type(self).__name__
+        # SB3's policy_kwargs["net_arch"]; None: the 128-unit net, as before the 64-unit form
+        self.hidden = HIDDEN if net_arch is None else net_arch_hidden(net_arch, who)
         if is_attention_policy(state_dict) or is_attention_ln_policy(state_dict):
             raise ValueError("%s updates the MlpPolicy; the attention policies' update is "
                              "not implemented" % who)
@@ -1227,7 +1267,7 @@ class _FusedLearner:
         self.collector = collector
         self.device = collector.device
         self.O, self.A = collector.O, collector.A
-        self.layout, self.P = a2c_param_layout(self.O, self.A)
+        self.layout, self.P = a2c_param_layout(self.O, self.A, self.hidden)
         flat = []
         for k, (_, shp) in self.layout.items():
             if k not in state_dict:
@@ -1235,7 +1275,7 @@ class _FusedLearner:
             t = torch.as_tensor(_np(state_dict[k]))
             if tuple(t.shape) != tuple(shp):
                 raise ValueError("%s has shape %s, expected %s (%s implements hidden=%d)"
-                                 % (k, tuple(t.shape), shp, who, HIDDEN))
+                                 % (k, tuple(t.shape), shp, who, self.hidden))
             flat.append(t.reshape(-1))
         self.params = torch.cat(flat).to(self.device).contiguous()
         self.learning_rate = learning_rate
@@ -1259,6 +1299,10 @@ class _FusedLearner:
     def state_dict(self):
         """SB3 keys -> float32 CPU tensors (one device-to-host copy)."""
         return self._by_key(self.params)
+
+    def _workspace_need(self, kind, n):
+        """Entries of the workspace a gradient launch on n samples needs."""
+        return _grad_fns(kind, self.hidden, self.O, self.A, type(self).__name__)[1](n, 0) // 8
 
     def _workspace(self, need):
         """The gradient kernels' float64 workspace, grown to `need` entries."""
@@ -1308,17 +1352,21 @@ class FusedA2C(_FusedLearner):
     through the host packer into the collector's blob (collector.set_params).
 
     learning_rate: a float or a schedule of SB3's progress_remaining (linear_schedule).
-    Float32 MlpPolicy collectors only; normalize_advantage and Adam are not implemented."""
+    net_arch: SB3's policy_kwargs["net_arch"] -- None (the 128-unit net), or 64 / [64, 64] /
+    dict(pi=[64, 64], vf=[64, 64]) for SB3's default MlpPolicy, which is what
+    code/lorenz_pmsm/train.py:130-139 trains (the same forms with 128 are accepted); the
+    state_dict must have that size.  Float32 MlpPolicy collectors only; normalize_advantage
+    and Adam are not implemented."""
 
     def __init__(self, collector, state_dict, learning_rate=7e-4, n_steps=5, vf_coef=0.5,
                  ent_coef=0.0, max_grad_norm=0.5, rms_prop_eps=1e-5, group=None,
-                 normalize_advantage=False, use_rms_prop=True):
+                 normalize_advantage=False, use_rms_prop=True, net_arch=None):
         if normalize_advantage:
             raise ValueError("FusedA2C: normalize_advantage is not implemented (SB3's default-off "
                              "option; the reference leaves it off)")
         if not use_rms_prop:
             raise ValueError("FusedA2C: only RMSpropTFLike (use_rms_prop=True) is implemented")
-        super().__init__(collector, state_dict, learning_rate, n_steps)
+        super().__init__(collector, state_dict, learning_rate, n_steps, net_arch)
         self.square_avg = torch.ones_like(self.params)  # RMSpropTFLike starts at ones
         self.vf_coef, self.ent_coef = float(vf_coef), float(ent_coef)
         self.max_grad_norm, self.rms_prop_eps = float(max_grad_norm), float(rms_prop_eps)
@@ -1338,9 +1386,10 @@ class FusedA2C(_FusedLearner):
             raise ValueError("FusedA2C.update: compute_returns_and_advantage(batch) first")
         lr = self._lr() if lr is None else float(lr)
         B = int(batch.advantages.numel())
-        ws = self._workspace(int(nat.lib.lz_a2c_workspace_bytes(B, self.O, self.A, 0)) // 8)
+        ws = self._workspace(self._workspace_need("a2c", B))
         a2c_grad(self.params, batch.observations, batch.actions, batch.advantages, batch.returns,
-                 self.O, self.A, self.vf_coef, self.ent_coef, workspace=ws, out=self._sums)
+                 self.O, self.A, self.vf_coef, self.ent_coef, workspace=ws, out=self._sums,
+                 hidden=self.hidden)
         if self.group is not None:
             dist.all_reduce(self._sums, group=self.group)
         stats = a2c_apply(self._sums, self.params, self.square_avg, lr, self.max_grad_norm, 0.99,
@@ -1389,7 +1438,7 @@ def ppo_adv_moments(advantages, indices=None, out=None):
 def ppo_grad(params, observations, actions, advantages, returns, old_log_prob, old_values, obs_dim,
              act_dim, indices=None, clip_range=0.2, clip_range_vf=None, adv_moments=None, ctrl=None,
              vf_coef=0.5, ent_coef=0.0, max_workgroups=0, workspace=None, out=None, hidden=HIDDEN):
-    """lz_ppo_grad_f32 on the current stream over the rows `indices` (int32 device tensor
+    """lz_ppo_grad_f32 (hidden=64: lz_ppo_grad_hidden_f32) on the current stream over the rows `indices` (int32 device tensor
     [M]; None: every row) of the flat rollout arrays: float64 device tensor [P + 6] of the
     gradient sums, then sum(policy loss terms), sum((ret - v_pred)^2), sum(-entropy), M,
     the clipped count and sum((ratio - 1) - log_ratio).  adv_moments: ppo_adv_moments'
@@ -1400,9 +1449,7 @@ def ppo_grad(params, observations, actions, advantages, returns, old_log_prob, o
     O, A = int(obs_dim), int(act_dim)
     if dev.type != "cuda":
         raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "ppo_grad: params must be a device tensor")
-    P = int(nat.lib.lz_a2c_param_count(O, A))
-    if P < 0:
-        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "ppo_grad: obs_dim must be 1..8, act_dim 1..4")
+    P, ws_bytes, grad_fn = _grad_fns("ppo", hidden, O, A, "ppo_grad")
     n_rows = int(advantages.numel())
     cvf = 0.0 if clip_range_vf is None else float(clip_range_vf)
     f32 = torch.float32
@@ -1421,7 +1468,7 @@ def ppo_grad(params, observations, actions, advantages, returns, old_log_prob, o
     g.clip_range, g.clip_range_vf = float(clip_range), cvf
     g.adv_moments = check_buffer(adv_moments, "adv_moments", torch.float64, 2, dev, required=False)
     g.ctrl = check_buffer(ctrl, "ctrl", torch.int64, 2, dev, required=False)
-    need = int(nat.lib.lz_ppo_workspace_bytes(M, O, A, int(max_workgroups)))
+    need = ws_bytes(M, int(max_workgroups))
     if need < 0:
         raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "ppo_grad: empty batch or bad max_workgroups")
     if workspace is None:
@@ -1431,7 +1478,7 @@ def ppo_grad(params, observations, actions, advantages, returns, old_log_prob, o
     if out is None:
         out = torch.empty((P + 6,), dtype=torch.float64, device=dev)
     g.grad_sums = check_buffer(out, "grad_sums", torch.float64, P + 6, dev)
-    nat.check(nat.lib.lz_ppo_grad_f32(ctypes.byref(g), dev.index, _stream_ptr(dev)))
+    nat.check(grad_fn(ctypes.byref(g), dev.index, _stream_ptr(dev)))
     return out
 
 
@@ -1474,17 +1521,20 @@ class FusedPPO(_FusedLearner):
 
     learning_rate, clip_range (and clip_range_vf): a float or a schedule of SB3's
     progress_remaining (linear_schedule).  generator: the torch.Generator (on the
-    collector's device) the permutations are drawn from.  Float32 MlpPolicy collectors only."""
+    collector's device) the permutations are drawn from.  net_arch: as FusedA2C's (64 is
+    what code/train.py:106-118 and code/lorenz_filter/train.py:117-129 train, and the size of
+    the reference's shipped PPO policies).  Float32 MlpPolicy collectors only."""
 
     def __init__(self, collector, state_dict, learning_rate=3e-4, n_steps=2048, batch_size=64,
                  n_epochs=10, clip_range=0.2, clip_range_vf=None, normalize_advantage=True,
-                 ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, target_kl=None, generator=None):
+                 ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, target_kl=None, generator=None,
+                 net_arch=None):
         if int(batch_size) < 1 or int(n_epochs) < 1 or int(n_steps) < 1:
             raise ValueError("FusedPPO: n_steps, batch_size and n_epochs must be >= 1")
         if normalize_advantage and int(batch_size) < 2:
             raise ValueError("FusedPPO: batch_size must be > 1 with normalize_advantage "
                              "(SB3 asserts it)")
-        super().__init__(collector, state_dict, learning_rate, n_steps)
+        super().__init__(collector, state_dict, learning_rate, n_steps, net_arch)
         dev = self.device
         self.exp_avg = torch.zeros_like(self.params)
         self.exp_avg_sq = torch.zeros_like(self.params)
@@ -1528,7 +1578,7 @@ class FusedPPO(_FusedLearner):
         dev = self.device
         B = int(batch.advantages.numel())
         cuts = self.minibatches(B)
-        self._workspace(int(nat.lib.lz_ppo_workspace_bytes(min(self.batch_size, B), self.O, self.A, 0)) // 8)
+        self._workspace(self._workspace_need("ppo", min(self.batch_size, B)))
         if self._perm is None or self._perm.numel() != B:
             self._perm = torch.empty((B,), dtype=torch.int32, device=dev)
         rows = self.n_epochs * len(cuts)
@@ -1563,7 +1613,8 @@ class FusedPPO(_FusedLearner):
             mom = ppo_adv_moments(batch.advantages, indices, out=self._mom)
         ppo_grad(self.params, batch.observations, batch.actions, batch.advantages, batch.returns,
                  batch.log_probs, batch.values, self.O, self.A, indices, clip_range, clip_range_vf, mom,
-                 self.ctrl, self.vf_coef, self.ent_coef, workspace=self._ws, out=self._sums)
+                 self.ctrl, self.vf_coef, self.ent_coef, workspace=self._ws, out=self._sums,
+                 hidden=self.hidden)
         adam_apply(self._sums, self.params, self.exp_avg, self.exp_avg_sq, self.ctrl, lr,
                    self.max_grad_norm, (0.9, 0.999), 1e-5, self.vf_coef, self.ent_coef, self.target_kl,
                    stats=stats_row)

@@ -54,6 +54,12 @@
  *       -> SB3 PPO.train() for the MlpPolicy: one clipped minibatch step, advantage
  *          normalisation, clip_grad_norm_ and Adam, the target_kl stop (code/train.py:97-129,
  *          code/lorenz_filter/train.py, code/gym_run.py:83)
+ *   lz_a2c_grad_hidden_f32 / lz_ppo_grad_hidden_f32 (lz_a2c_param_count_hidden,
+ *   lz_a2c_workspace_bytes_hidden, lz_ppo_workspace_bytes_hidden)
+ *       -> the same two updates for SB3's default 64 x 64 MlpPolicy, which is what those
+ *          scripts train when no policy_kwargs reach the constructor (code/train.py:106-118,
+ *          code/lorenz_filter/train.py:117-129, code/lorenz_pmsm/train.py:130-139,
+ *          code/lorenz_pmsm/optimize.py:38-42 net_dim 64)
  *   lz_attn_policy_pack / lz_rollout_policy_attn
  *       -> the same for code/train.py:52-112 and code/gym_try.py:52-116 (PPO with the
  *          AttentionFeaturesExtractor)
@@ -793,7 +799,7 @@ typedef struct lz_a2c_grad_args {
   int64_t n_samples;          /* B >= 1 */
   int32_t obs_dim;            /* 1..8 */
   int32_t act_dim;            /* 1..4 */
-  int32_t hidden;             /* 128 */
+  int32_t hidden;             /* 128 (lz_a2c_grad_hidden_f32: 128 or 64) */
   int32_t max_workgroups;     /* cap on the workgroups per net (tests: forces the grid-stride
                                  loop at small B); 0 = the default, 128 */
   double vf_coef, ent_coef;
@@ -820,6 +826,25 @@ int64_t lz_a2c_workspace_bytes(int64_t n_samples, int32_t obs_dim, int32_t act_d
                                int32_t max_workgroups);
 lz_status lz_a2c_grad_f32(const lz_a2c_grad_args* g, int32_t device, void* hip_stream);
 lz_status lz_a2c_apply_f32(const lz_a2c_apply_args* a, int32_t device, void* hip_stream);
+
+/* The same gradient step for a net of `hidden` units per layer (named as
+ * lz_policy_pack_hidden): 128 as above, or 64 -- SB3's default MlpPolicy, which is what the
+ * reference's A2C learner trains (code/lorenz_pmsm/train.py:130-139: its policy_kwargs are
+ * commented out) and half of code/lorenz_pmsm/optimize.py:38-42's trials (net_dim in
+ * {64, 128}).  The flat vector has the layout above with `hidden` in place of 128:
+ *   P = 2 (H O + H + H^2 + H) + A H + A + H + 1 + A        (9,413 at O = 6, A = 2, H = 64)
+ * lz_a2c_param_count_hidden and lz_a2c_workspace_bytes_hidden return -1 for any other
+ * hidden; at 128 they equal the functions above.  lz_a2c_grad_hidden_f32 takes the same
+ * struct: hidden == 128 launches the same kernel as lz_a2c_grad_f32 (the same bits),
+ * hidden == 64 the 64-unit form of the same kernel text (2 waves per workgroup; what the
+ * 128-unit kernel computes on the zero-padded net, value for value), anything else is
+ * LZ_ERR_UNSUPPORTED.  Every other refusal is lz_a2c_grad_f32's, in its order; the workspace
+ * is checked against lz_a2c_workspace_bytes_hidden.  lz_a2c_apply_f32 takes lengths and
+ * serves both.  Host-only size functions. */
+int64_t lz_a2c_param_count_hidden(int32_t obs_dim, int32_t act_dim, int32_t hidden);
+int64_t lz_a2c_workspace_bytes_hidden(int64_t n_samples, int32_t obs_dim, int32_t act_dim,
+                                      int32_t hidden, int32_t max_workgroups);
+lz_status lz_a2c_grad_hidden_f32(const lz_a2c_grad_args* g, int32_t device, void* hip_stream);
 
 /* ------------------------------------------------------------------------------
  * One PPO minibatch step for the same float32 MlpPolicy: SB3 2.7.1 PPO.train()
@@ -899,7 +924,7 @@ typedef struct lz_ppo_grad_args {
   int64_t n_samples;          /* M >= 1 */
   int32_t obs_dim;            /* 1..8 */
   int32_t act_dim;            /* 1..4 */
-  int32_t hidden;             /* 128 */
+  int32_t hidden;             /* 128 (lz_ppo_grad_hidden_f32: 128 or 64) */
   int32_t max_workgroups;     /* as lz_a2c_grad_args */
   double vf_coef, ent_coef;
   void* workspace;            /* device, >= lz_ppo_workspace_bytes(...) bytes */
@@ -937,6 +962,20 @@ lz_status lz_ppo_adv_moments(const float* advantages, const int32_t* indices, in
                              void* hip_stream);
 lz_status lz_ppo_grad_f32(const lz_ppo_grad_args* g, int32_t device, void* hip_stream);
 lz_status lz_adam_apply_f32(const lz_adam_apply_args* a, int32_t device, void* hip_stream);
+
+/* The same minibatch gradient for a net of `hidden` units per layer, as
+ * lz_a2c_grad_hidden_f32: 128, or 64 -- SB3's default MlpPolicy, which is what the
+ * reference's PPO scripts train (code/train.py:106-118 and code/lorenz_filter/train.py:
+ * 117-129 build a policy_kwargs dict and never pass it to the constructor) and what its
+ * shipped PPO policies hold (hr_sync_agent.zip: (64, 6) / (64, 64) / (1, 64)).  params
+ * is [lz_a2c_param_count_hidden], grad_sums [that + 6].  hidden == 128 launches the same
+ * kernel as lz_ppo_grad_f32 (the same bits), hidden == 64 the 64-unit form, anything else
+ * is LZ_ERR_UNSUPPORTED; every other refusal is lz_ppo_grad_f32's, in its order, with the
+ * workspace checked against lz_ppo_workspace_bytes_hidden (-1 for any other hidden).
+ * lz_ppo_adv_moments and lz_adam_apply_f32 serve both. */
+int64_t lz_ppo_workspace_bytes_hidden(int64_t n_samples, int32_t obs_dim, int32_t act_dim,
+                                      int32_t hidden, int32_t max_workgroups);
+lz_status lz_ppo_grad_hidden_f32(const lz_ppo_grad_args* g, int32_t device, void* hip_stream);
 
 /* RolloutBuffer.episode_starts of one collect (SB3 2.7.1 OnPolicyAlgorithm.
  * collect_rollouts: rollout_buffer.add(..., self._last_episode_starts, ...), then
