@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 import torch
 
+import device_normals as dn
 from conftest import bits_equal
 
 pytestmark = pytest.mark.gpu
@@ -168,6 +169,11 @@ def test_attn_f32_bootstrap_and_sampling(gl, pol, orc):
     scale, var2, lscale = f[4:8], f[8:12], f[12:16]
     z = (act - mean) / scale[:2]
     assert abs(z.mean()) < 0.03 and abs(z.std() - 1.0) < 0.03
+    # ... and sample by sample the normal of (seed, env, tick = step + 1)
+    for k in range(K):
+        r = slice(k * n, (k + 1) * n)
+        dn.check_action(act[r], mean[r], scale[:2], orc.policy_normals(21, np.arange(n), k + 1)[:, :2],
+                        "step %d" % k)
     dd = (act - mean).astype(np.float32)
     lp = None
     for j in range(2):

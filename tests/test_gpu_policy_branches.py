@@ -31,13 +31,15 @@ Branches (MI355X: 256 CUs):
                   its smallest size (33 / 17 envs; 129 = four split tiles plus one; 65,536 /
                   131,072 where only the size picks the kernel), with sampled actions, the
                   truncation bootstrap and 2-step episodes; those rows also check the
-                  log-probs and the bootstrapped rewards, and the ones above 20,000 recorded
+                  log-probs, on the exact kinds every sample against the normal its Philox
+                  stream prescribes, and the bootstrapped rewards, and the ones above 20,000 recorded
                   rows check the forward on 6,000 sampled rows plus the ragged tail
 """
 import numpy as np
 import pytest
 import torch
 
+import device_normals as dn
 from conftest import bits_equal
 
 pytestmark = pytest.mark.gpu
@@ -233,6 +235,7 @@ def test_policy_branch(gl, pol, orc, kind, system, n, K, variant, n_stack, kerne
     act = _np(b.actions).reshape(-1, A)
     val = _np(b.values).reshape(-1)
     logp = _np(b.log_probs).reshape(-1)
+    rows = np.arange(x.shape[0])  # row r = (step r // n, env r % n)
     if sampled and x.shape[0] > 20000:  # sampled rows and the ragged tail
         rows = np.concatenate([np.random.default_rng(0).choice(x.shape[0], 6000, replace=False),
                                np.arange(x.shape[0] - 70, x.shape[0])])
@@ -260,14 +263,19 @@ def test_policy_branch(gl, pol, orc, kind, system, n, K, variant, n_stack, kerne
         np.testing.assert_allclose(val[f], _np(vt)[f], atol=tol, rtol=tol)
         assert np.median(np.abs(val[f] - _np(vt)[f])) < 2e-3
     if sampled:
-        _check_sampled(pol, orc, kind, exact, sd, col, b, x, act, mref, logp, trunc, _np(rew_r), n, O, A)
+        _check_sampled(pol, orc, kind, exact, sd, col, b, x, act, mref, logp, trunc, _np(rew_r), n, O, A,
+                       rows, "%s-%s-%d" % (kind, system, n))
     envp.close()
     envr.close()
 
 
-def _check_sampled(pol, orc, kind, exact, sd, col, b, x, act, mref, logp, trunc, rew_r, n, O, A):
+def _check_sampled(pol, orc, kind, exact, sd, col, b, x, act, mref, logp, trunc, rew_r, n, O, A, rows, what):
     """The sampled rows' extra checks: the noise z = (action - mean) / scale is finite and
-    differs between rows (env, step: the Philox counter); the log-prob is the kernel's formula
+    differs between rows (env, step: the Philox counter) and, on the exact kinds (mref is the
+    oracle's bit-exact mean, the scale the blob's), it is the normal the Philox stream
+    prescribes for the row's (step, env) = divmod(rows, n): oracle.policy_normals(seed 5, env,
+    tick = step + 1) under tests/device_normals.py's check_action, on every finite row, which
+    at least 90 % of a case's rows must be; the log-prob is the kernel's formula
     on action - mean, bit for bit on the float32 kinds (the blob's Normal constants), within
     tests/test_gpu_policy.py's tolerance of torch's Normal on the bf16 ones; every truncated
     step's reward is the env's plus gamma * V(stacked terminal observation)."""
@@ -281,6 +289,13 @@ def _check_sampled(pol, orc, kind, exact, sd, col, b, x, act, mref, logp, trunc,
     z = (act - mref)[f] / scale[:A]
     assert np.isfinite(z).all() and len(np.unique(z[:, 0])) > 0.9 * len(z)
     if exact:
+        assert f.mean() >= 0.9, (what, f.mean())
+        step, env = np.divmod(rows[f], n)
+        zp = np.empty((len(step), A))
+        for k in np.unique(step):  # one collect after reset(): step k draws at tick k + 1
+            zp[step == k] = orc.policy_normals(5, env[step == k], int(k) + 1)[:, :A]
+        worst = dn.check_action(act[f], mref[f], scale[:A], zp, what)
+        print("sampled rows %s: worst err / tol %.3f (%d of %d rows finite)" % (what, worst, f.sum(), f.size))
         dd = (act - mref).astype(np.float32)
         lp = None
         for j in range(A):

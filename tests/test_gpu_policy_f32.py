@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 import torch
 
+import device_normals as dn
 from test_policy_f32_host import GOLD, normalize_obs, oracle_closed_loop
 
 pytestmark = pytest.mark.gpu
@@ -164,6 +165,11 @@ def test_f32_sampling_and_log_prob(gl, pol, orc):
     z = (act - mean) / scale[:2]
     assert abs(z.mean()) < 0.01 and abs(z.std() - 1.0) < 0.01
     assert abs(np.corrcoef(z[:, 0], z[:, 1])[0, 1]) < 0.01
+    # ... and sample by sample the normal of (seed, env, tick = step + 1)
+    for k in range(K):
+        r = slice(k * n, (k + 1) * n)
+        dn.check_action(act[r], mean[r], scale[:2], orc.policy_normals(9, np.arange(n), k + 1)[:, :2],
+                        "step %d" % k)
     d = (act - mean).astype(np.float32)
     assert np.array_equal(_np(b.log_probs).reshape(-1), _logp(d, var2, lscale, 2))
     lp_torch = torch.distributions.Normal(torch.from_numpy(mean), torch.exp(sd["log_std"])).log_prob(
