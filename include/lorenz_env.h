@@ -92,8 +92,31 @@
  *   - hipGraph capture: lz_reset / lz_step / lz_rollout enqueue kernels (and, for
  *     n_done_out, one D2D copy) only -- no allocation, no host sync -- and keep their
  *     RNG call counter and compact-list cursor in device memory (2-slot ping-pong
- *     selected by a host-side call parity).  A captured sequence must therefore hold
- *     an EVEN number of these calls so that every replay starts on the same slot.
+ *     selected by a host-side call parity: a launch reads slot p and writes the advanced
+ *     counter and a zeroed cursor into slot 1 - p; p is frozen into the captured node).
+ *     "These calls" are the ones that flip the parity: lz_reset, lz_step, lz_step_vecnorm
+ *     (its lz_vecnorm_apply does not), lz_rollout, the policy rollouts, every step k < K
+ *     of lz_policy_step_f32 and the evaluators.  The contract has two halves:
+ *       (1) a captured sequence holds an EVEN number of these calls, so that it ends on
+ *           the slot it began on and every replay continues its predecessor;
+ *       (2) a replay must BEGIN with the handle on the parity the capture began on: an
+ *           even number of eager calls (or none) between the capture and a replay and
+ *           between two replays.
+ *     With both kept, replays and eager calls on the handle interleave freely and give
+ *     the bits of the same calls made eagerly (tests/test_gpu_graph_replay.py: three
+ *     replays with eager calls in between, every system family, lz_reset(mask), lz_step,
+ *     lz_rollout and the lz_step_vecnorm pair, against the CPU oracle or an eager twin).
+ *     A capture runs nothing but does flip the host parity once per captured call.  After
+ *     an even-length capture the handle is back on the parity it began on, so eager calls
+ *     go on whether or not the graph is ever replayed.  After an ODD-length capture the
+ *     host parity has moved while the device has not: the next eager call reads the stale
+ *     slot (the previous call's tick), and every replay after the first re-reads the tick
+ *     its predecessor read -- auto-resets redraw the same states, process noise repeats,
+ *     and no error is raised.  Neither half is checked by the library: a replay does not
+ *     pass through it, and seeing (1) at the first call after a capture takes a stream
+ *     query (hipStreamGetCaptureInfo) in every eager call, which was measured and costs
+ *     more than the eager launch path may lose.  Both halves are the
+ *     caller's to keep: count the calls.
  */
 #ifndef LORENZ_ENV_H
 #define LORENZ_ENV_H
@@ -1085,7 +1108,12 @@ typedef struct lz_vecnorm {
 /* lz_step's contract for the raw outputs (obs_out/rew_out/done/compact list) plus the
  * VecNormalize bookkeeping above.  n_done_out (device int32) is required: the compact
  * list is how lz_vecnorm_apply finds the terminal rows to normalise; it is written by
- * the paired lz_vecnorm_apply launch (LZ_VN_DEFER: by this call's second launch). */
+ * the paired lz_vecnorm_apply launch (LZ_VN_DEFER: by this call's second launch).
+ * The first call on a handle allocates its moment workspace (do not capture that first
+ * call: take one eager pair before capturing a sequence of pairs).  One pair is ONE
+ * parity-flipping call of the hipGraph note above (lz_vecnorm_apply flips nothing); the
+ * RunningMeanStd states, `returns` and the moment partials all live on the device, so
+ * replayed pairs accumulate exactly as eager ones (tests/test_gpu_graph_replay.py). */
 lz_status lz_step_vecnorm(lz_handle* h, const lz_vecnorm* vn, const void* actions,
                           void* obs_out, void* rew_out, uint8_t* done_out, int32_t* done_idx_out,
                           void* terminal_obs_out, int32_t* n_done_out);
