@@ -51,6 +51,82 @@ struct KArgs {
   double prm[LZ_MAX_PARAMS];
 };
 
+// The tuning variant word (KArgs::variant = lz_config.reserved[0], default 0).  Every bit
+// keeps its value: tests, bench.py --variant and tools/ab_*.py pass numbers.  Only LORENZ3
+// float32 and PMSM instantiate the step variants and the prefetch distances (kVariants,
+// lz_kernels.hip); the other systems ignore those bits.
+//
+//   bit(s)  value     name                 selects                                  read by
+//   0       1         kVarStepPlain        plain (temporal) act/obs/rew/done I/O    step (A/B only)
+//   1       2         kVarStepDirect       lanes access their own act/obs rows      step (A/B only)
+//   2       4         kVarStepFullBar      __syncthreads() at the LDS hand-offs     step (A/B only)
+//   3-4     8/16/24   kVarStepBlock*       512 / 128 / 1024 envs per workgroup      step (A/B only)
+//   5       32        kVarStepDoneT        temporal done-byte stores                step (A/B only)
+//   5       32        kVarPolSerial        bf16 MlpPolicy: (32, 8, serial) shape    policy_shape (A/B only)
+//   6       64        kVarPolInterleaved   bf16 MlpPolicy: interleaved nets         policy_shape (A/B only)
+//   7       128       kVarPolNoPipe        ... without the pipelined weight loads   policy_shape (A/B only)
+//   8       256       kVarOneLane          one lane per env (no split lanes)        rollout_plan
+//   9       512       kVarTwoLanes         two lanes per env (split lanes)          rollout_plan
+//   10      1024      kVarDist3            prefetch distance D = 3                  rollout_plan (A/B only)
+//   11      2048      kVarKeepDone         keep the done path (no done-free kernel) rollout_plan (A/B only)
+//   12      4096      kVarSplitDist15      split lanes / lane pair: D = 15          rollout_plan (A/B only)
+//   13      8192      kVarPolF32OneWave    float32 MlpPolicy: the one-wave kernel   f32_policy_shape (A/B only)
+//   14-15   16384 x   kVarTiles*           step tiles per workgroup: 1 / 2 / 4      step_tiles
+//   18-20   1 << 18 x kVarSplitSv*         done-free split kernel's store policy:   rollout_plan (A/B only)
+//                                          selector 1, 3, 4, 7 -> SV 0, 3, 5, 7
+//   21      1 << 21   kVarDoneNT           non-temporal done bytes, 256-lane kernel rollout_plan (A/B only)
+//   22      1 << 22   kVarMultiDoneT       temporal done bytes, k_step_multi<4>     step (A/B only)
+//   23      1 << 23   kVarForceBlock       the 256-lane rollout at any N            rollout_plan
+//   24      1 << 24   kVarForceWave        one-wave groups at any N                 rollout_plan
+//   25      1 << 25   kVarProducer         one-wave groups + noise-producer wave    rollout_plan (A/B only)
+//   26      1 << 26   kVarZN               next step's normals drawn a step ahead   rollout_plan (A/B only)
+//   27      1 << 27   kVarForcePair        the PMSM lane pair at any N              rollout_plan
+//   28      1 << 28   kVarNoPair           never the lane pair                      rollout_plan
+//
+// Overlap: the step launch reads bits 0-5 as ONE number (kVarStepMask), the policy shape
+// functions read 32 / 64 / 128 / 8192 of the same word -- bit 5 means "temporal done
+// stores" to lz_step and "(32, 8, serial)" to the bf16 policy rollout.  A handle runs one
+// or the other launch with a given word, so the A/B tools set the bit for one at a time.
+// Bits 16-17 and 29-31 are unused.
+enum Variant : int32_t {
+  kVarStepPlain = 1,
+  kVarStepDirect = 2,
+  kVarStepFullBar = 4,
+  kVarStepBlockShift = 3,  // bits 3-4: 0 = 256 envs per workgroup
+  kVarStepBlockMask = 3,
+  kVarStepBlock512 = 1 << kVarStepBlockShift,
+  kVarStepBlock128 = 2 << kVarStepBlockShift,
+  kVarStepBlock1024 = 3 << kVarStepBlockShift,
+  kVarStepDoneT = 32,
+  kVarStepMask = 63,
+  kVarPolSerial = 32,
+  kVarPolInterleaved = 64,
+  kVarPolNoPipe = 128,
+  kVarOneLane = 256,
+  kVarTwoLanes = 512,
+  kVarDist3 = 1024,
+  kVarKeepDone = 2048,
+  kVarSplitDist15 = 4096,
+  kVarPolF32OneWave = 8192,
+  kVarTilesShift = 14,  // bits 14-15: 0 = the measured default (step_tiles_balanced)
+  kVarTilesMask = 3,
+  kVarTiles1 = 1,
+  kVarTiles2 = 2,
+  kVarTiles4 = 3,
+  kVarSplitSvShift = 18,  // bits 18-20: 0 (and 2, 5, 6) = the default SV = 1
+  kVarSplitSvMask = 7,
+  kVarDoneNT = 1 << 21,
+  kVarMultiDoneT = 1 << 22,
+  kVarForceBlock = 1 << 23,
+  kVarForceWave = 1 << 24,
+  kVarProducer = 1 << 25,
+  kVarZN = 1 << 26,
+  kVarForcePair = 1 << 27,
+  kVarNoPair = 1 << 28,
+  // any of these names another rollout kernel: the lane pair's default steps aside
+  kVarOtherRollout = kVarOneLane | kVarTwoLanes | kVarForceBlock | kVarForceWave | kVarProducer | kVarZN,
+};
+
 // VecNormalize epilogue of the step kernel (lz_step_vecnorm).  Per-workgroup float64
 // partials of the batch moments, column-major [W][n_wg] with W = 2 (O + 1) columns:
 // sums of obs column 0..O-1, of the returns, then the sums of squares likewise;
@@ -546,8 +622,9 @@ typedef PolShape (*PolShapeFn)(int64_t n, int num_cus, int variant);
 inline PolShape policy_shape(int64_t n, int num_cus, int variant) {
   PolShape s;
   const int64_t waves32 = (n + 31) / 32;
-  if (variant & 32) s = {32, 8, 0, 0};
-  else if ((variant & 64) || waves32 < 8 * (int64_t)num_cus) s = {32, 4, (variant & 128) ? 1 : 2, 0};
+  if (variant & kVarPolSerial) s = {32, 8, 0, 0};
+  else if ((variant & kVarPolInterleaved) || waves32 < 8 * (int64_t)num_cus)
+    s = {32, 4, (variant & kVarPolNoPipe) ? 1 : 2, 0};
   else if (n < 131072) s = {32, 8, 0, 0};
   else s = {64, 8, 0, 0};
   const int64_t groups = ((n + s.envs_per_wave - 1) / s.envs_per_wave + s.waves - 1) / s.waves;

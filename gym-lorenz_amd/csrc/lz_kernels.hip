@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "lz_act_ring.h"
 #include "lz_body.h"
 #include "lz_dispatch.h"
 #include "lz_internal.h"
@@ -114,7 +115,8 @@ __global__ __launch_bounds__(kBlock) void k_reset(KArgs a) {
 // faster than plain, LDS staging 7-11% faster than direct.
 template <int V>
 constexpr int step_block() {  // bits 3-4 of V: workgroup size
-  return ((V >> 3) & 3) == 1 ? 512 : ((V >> 3) & 3) == 2 ? 128 : ((V >> 3) & 3) == 3 ? 1024 : 256;
+  constexpr int b = V & (kVarStepBlockMask << kVarStepBlockShift);
+  return b == kVarStepBlock512 ? 512 : b == kVarStepBlock128 ? 128 : b == kVarStepBlock1024 ? 1024 : 256;
 }
 
 // ------------------------------------------------------------------ VecNormalize epilogue
@@ -244,10 +246,10 @@ __global__ __launch_bounds__(kVnColBlock) void k_vn_colsum(VArgs v, int64_t n,
 template <class Sys, typename T, int V, bool kVN>
 __device__ __forceinline__ void step_tile(const KArgs& a, const VArgs& v) {
   constexpr int SB = step_block<V>();
-  constexpr bool NT = (V & 1) == 0;
-  constexpr bool kLds = (V & 2) == 0;
-  constexpr bool kFullBar = (V & 4) != 0;
-  constexpr bool kDoneT = (V & 32) != 0;  // A/B: temporal done-byte stores
+  constexpr bool NT = (V & kVarStepPlain) == 0;
+  constexpr bool kLds = (V & kVarStepDirect) == 0;
+  constexpr bool kFullBar = (V & kVarStepFullBar) != 0;
+  constexpr bool kDoneT = (V & kVarStepDoneT) != 0;  // A/B: temporal done-byte stores
   __shared__ __attribute__((aligned(16))) float s_act[kLds ? SB * Sys::A : 4];
   __shared__ __attribute__((aligned(16))) T s_obs[kLds ? SB * Sys::O : 2];
   const int tid = (int)threadIdx.x;
@@ -545,10 +547,10 @@ inline int step_tiles_balanced(int64_t n, int num_cus, bool three) {
 template <class Sys>
 inline int step_tiles(const KArgs& a) {
   if (a.noise) return 1;  // injected noise: k_step (k_step_multi draws its noise on device)
-  switch ((a.variant >> 14) & 3) {
-    case 1: return 1;
-    case 2: return 2;
-    case 3: return 4;
+  switch ((a.variant >> kVarTilesShift) & kVarTilesMask) {
+    case kVarTiles1: return 1;
+    case kVarTiles2: return 2;
+    case kVarTiles4: return 4;
     default:
       return step_tiles_balanced(a.n, a.num_cus > 0 ? a.num_cus : 256, !std::is_same<Sys, SysHR<float>>::value);
   }
@@ -566,100 +568,6 @@ inline int step_tiles(const KArgs& a) {
 // registers.  With no exec-masked stores the compiler can count the vector-memory
 // ops issued after the prefetch and wait for the prefetch alone (vmcnt(N)) instead
 // of for every outstanding store (vmcnt(0)) -- a store-ack round trip per step.
-typedef float f2v __attribute__((ext_vector_type(2)));
-template <int RB>
-struct Chunk {  // widest power-of-two chunk (<= 16 B) that tiles a RB-byte row
-  using t = typename std::conditional<RB % 16 == 0, f4v,
-                                      typename std::conditional<RB % 8 == 0, f2v, float>::type>::type;
-  static constexpr int N = RB / (int)sizeof(t);
-};
-
-// Action prefetch by LDS-DMA (global_load_lds_dword, non-temporal), issued from inline
-// asm: the data lands in LDS without a VGPR destination and hipcc does not see the
-// DMA at all -- so it neither drains vmcnt(0) before later LDS reads (its LDS-DMA
-// alias rule) nor before reusing the address VGPRs, both of which it does for the
-// builtin.  The loop waits explicitly with vmcnt(N), N = the vector-memory
-// instructions it knows were issued after the DMA; older stores stay in flight.
-// Destination = M0 (wave-uniform LDS byte offset) + lane * 4.
-typedef __attribute__((address_space(3))) void* las_t;
-__device__ __forceinline__ uint32_t lds_off(const float* p) {
-  return (uint32_t)(uintptr_t)(las_t)(const_cast<float*>(p));
-}
-__device__ __forceinline__ void dma4_nt(const float* g, uint32_t m0) {
-  uint32_t saved;  // M0 is a reserved register hipcc may hold a value in: save/restore
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\tglobal_load_lds_dword %1, off nt\n\t"
-               "s_mov_b32 m0, %0"
-               : "=&s"(saved)
-               : "v"(g), "s"(m0)
-               : "memory");
-}
-// 16-B LDS-DMA (global_load_lds_dwordx4); the s_nop separates the M0 write from the
-// DMA that reads it.
-__device__ __forceinline__ void dma16_nt(const float* g, uint32_t m0) {
-  uint32_t saved;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\t"
-               "s_mov_b32 m0, %0"
-               : "=&s"(saved)
-               : "v"(g), "s"(m0)
-               : "memory");
-}
-// Row DMA of the fused rollout: ONE 16-B LDS-DMA per wave and step moves the wave's
-// contiguous [envs, A] action slice (envs = 64, or 32 in the split-lane kernel) into the
-// wave's own 1-KiB LDS region, row-major: lane l loads 16-B chunk l mod C of the slice
-// (C = envs * A / 4 chunks; the remaining lanes repeat chunks, so no lane reads past
-// the slice), landing at region + 16 l.  Needs the slice 16-B aligned (the launch's
-// vec_ok: actions 16-B aligned, N a multiple of 4) and envs * A a multiple of 4.
-template <int A, int E>
-constexpr bool row_dma() { return (A == 2 || A == 3) && (E * A) % 4 == 0; }
-constexpr int kRowRegionF = 256;  // floats per wave region and slot (64 lanes x 16 B)
-// LDS floats of the DMA ring per slot for a B-lane workgroup
-template <int A, int B>
-constexpr int act_slot_floats() { return row_dma<A, 64>() ? (B / 64) * kRowRegionF : B * A; }
-// LDS reads of the DMA'd slot, also from asm (with their own lgkmcnt wait), so that
-// no compiler-visible LDS access depends on the hidden DMA.
-template <int A>
-__device__ __forceinline__ void lds_read_act(float* act, const float* p0, int stride) {
-  if constexpr (A == 3) {
-    asm volatile("ds_read_b32 %0, %3\n\tds_read_b32 %1, %4\n\tds_read_b32 %2, %5\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&v"(act[0]), "=&v"(act[1]), "=&v"(act[2])
-                 : "v"(lds_off(p0)), "v"(lds_off(p0 + stride)), "v"(lds_off(p0 + 2 * stride))
-                 : "memory");
-  } else {
-    static_assert(A == 2, "action dim");
-    asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %3\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&v"(act[0]), "=&v"(act[1])
-                 : "v"(lds_off(p0)), "v"(lds_off(p0 + stride))
-                 : "memory");
-  }
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N <= 63, "vmcnt immediate (6 bits on gfx9)");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// Prefetch distance D of the fused rollout's action DMA (steps in flight; D + 1 LDS
-// slots, a power of two).  vmcnt counts stores as well as loads, so D also bounds how
-// many steps of stores stay in flight behind the wait at the top of a step.
-// D = 7 measured against 3 (tools/ab_rollout.py, K = 2048): LORENZ3 f32 +5% at 32,768
-// envs (split lanes), +1.5% at 262,144; PMSM +4% at 32,768, even at 262,144.
-constexpr int kDmaDist = 7;
-template <int D>
-constexpr int dma_slots() { return D + 1; }
-
-// vmcnt wait at the top of step k < D: the vector-memory ops issued after step k's
-// DMA are the prologue's later DMAs ((D-1-k) * kA) and k earlier steps' DMA + stores
-template <int D, int kA, int kSt, int J = 0>
-__device__ __forceinline__ void ladder_wait(int k) {
-  if constexpr (J < D) {
-    if (k == J) {
-      wait_vmcnt<(D - 1 - J) * kA + J * (kA + kSt)>();
-      return;
-    }
-    ladder_wait<D, kA, kSt, J + 1>(k);
-  }
-}
-
 constexpr int kZSlots = 4;  // steps of normals a producer wave may draw ahead (k_rollout kNP)
 constexpr uint32_t kZSpinCap = 1u << 24;  // polls of one flag before a wave gives up (~1 s)
 // LZ_RAG: which systems' ragged last group takes the full path (kRag): 2 (default) the
@@ -706,53 +614,26 @@ __device__ __forceinline__ void rollout_loop(Sys& sys, int32_t& steps, bool& any
   // row, which hipcc may merge into ceil(row/16) stores.  A LOWER bound is safe.
   constexpr int kRowB = Sys::O * (int)sizeof(T);
   constexpr int kSt = 2 + (kDirect ? (kRowB + 15) / 16 : CO::N);
+  // the action ring (lz_act_ring.h): row DMA where the wave's slice allows it, else one
+  // 4-B DMA per component -- component-major for one-wave groups, a verbatim copy of the
+  // row-major slice for staged 256-lane groups
   constexpr bool kRow = row_dma<Sys::A, 64>();
-  constexpr int kA = kRow ? 1 : Sys::A;  // DMA instructions per step
-  constexpr int kSlotF = act_slot_floats<Sys::A, B>();
+  using Ring = ActRing<Sys::A, 64, B, D, kSt,
+                       kRow ? ActLayout::Row : kDirect ? ActLayout::Direct : ActLayout::Staged>;
   const int lane = tid & 63;
-  // steady-state wait: step k's DMA has one step's stores plus D-1 steps' (DMA +
-  // stores) issued after it (lower bounds, see kSt)
-  constexpr int kSteady = kSt + (D - 1) * (kA + kSt);
-  static_assert(D >= 1 && kSteady <= 63, "vmcnt immediate (6 bits on gfx9)");
-  constexpr int kDmaSlots = dma_slots<D>();
-  // DMA step kk's action slice into LDS slot `slot` (B*A floats):
-  // direct: component-major [A][B]; staged: a verbatim copy of the row-major slice.
-  // src = this lane's first source float of step kk (component j is j, resp. j*B, on).
-  // M0 = LDS byte address of this wave's 64 destination floats: computed once,
-  // wave-uniform, then constant offsets per slot / component (no per-DMA address-space
-  // cast or readfirstlane)
-  const uint32_t m0_wave = __builtin_amdgcn_readfirstlane(
-      lds_off(s_act) + (uint32_t)wave * (kRow ? kRowRegionF * 4u : 256u));
-  auto issue = [&](const float* src, int slot) __attribute__((always_inline)) {
-    if constexpr (kRow) {
-      dma16_nt(src, m0_wave + (uint32_t)(slot * kSlotF) * 4u);
-    } else {
-#pragma unroll
-      for (int j = 0; j < Sys::A; ++j)
-        dma4_nt(src + (kDirect ? j : j * B), m0_wave + (uint32_t)((slot * Sys::A + j) * B) * 4u);
-    }
-  };
-  // this lane's DMA source pointer for step kk, and the per-step advance
+  const uint32_t m0_wave = Ring::wave_m0(s_act, wave);
+  // this lane's first source float of step 0
   const int64_t wave_row0 = (base + 64 * (int64_t)wave) * Sys::A;  // the wave's slice
-  const int lane_src = kRag ? (kRow ? min(lane % (64 * Sys::A / 4), nb * Sys::A / 4 - 1) : min(tid, nb - 1))
-                            : (kRow ? lane % (64 * Sys::A / 4) : tid);
+  const int lane_src = kRow ? Ring::template src_chunk<kRag>(lane, nb) : Ring::template src_row<kRag>(tid, nb);
   const int64_t lane0 = kRow ? wave_row0 + 4 * lane_src
                              : kDirect ? (base + lane_src) * Sys::A : base * Sys::A + tid;
   const int64_t dstride = a.n * Sys::A;
-  auto dma_src = [&](int kk) __attribute__((always_inline)) {
-    return gact + ((int64_t)kk * dstride + lane0);
-  };
   // settle every compiler-visible load of the prologue (state planes) here, so that
   // hipcc's wait bookkeeping enters the loop with nothing pending and emits no drain
   // inside it (vmcnt(0) alone: 0x0F70 = expcnt 7, lgkmcnt 15, vmcnt 0)
   if constexpr (FULL) __builtin_amdgcn_s_waitcnt(0x0F70);
-  if constexpr (FULL && Sys::kUsesAction) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) issue(dma_src(d < a.K ? d : a.K - 1), d);
-  }
-  // running source of the DMA issued at step k (step min(k + D, K - 1)): advanced by
-  // one step per step until it reaches the last (no per-step 64-bit multiply)
-  const float* dsrc = dma_src(D < a.K ? D : a.K - 1);
+  const float* dsrc = nullptr;  // the running DMA source (Ring::fill / Ring::refill)
+  if constexpr (FULL && Sys::kUsesAction) dsrc = Ring::fill(gact, lane0, dstride, a.K, m0_wave);
   uint32_t zcap = 0;  // kNP: the producer timed out once -- stop waiting for it (sticky)
   // kZN: step k's normals, drawn during step k - 1 (step 0's here); see step_body kZMode 2
   float zn[3] = {0.0f, 0.0f, 0.0f};
@@ -767,12 +648,11 @@ __device__ __forceinline__ void rollout_loop(Sys& sys, int32_t& steps, bool& any
     float act[Sys::A];
     if constexpr (Sys::kUsesAction) {
       if constexpr (FULL) {
-        if constexpr (decltype(ladder)::value) ladder_wait<D, kA, kSt>(k);
-        else wait_vmcnt<kSteady>();
+        Ring::template wait<decltype(ladder)::value>(k);
         // staged path: every wave is past the previous step's reads of s_obs (and, without
         // row DMA, every wave's DMA of this slot has landed)
         if constexpr (!kDirect) wg_barrier<false>();
-        const float* slot = s_act + (k % kDmaSlots) * kSlotF;
+        const float* slot = Ring::slot(s_act, k);
         if constexpr (kRow) {  // ordinary LDS loads: ordered after the wait by its clobber
 #pragma unroll
           for (int j = 0; j < Sys::A; ++j)
@@ -782,29 +662,12 @@ __device__ __forceinline__ void rollout_loop(Sys& sys, int32_t& steps, bool& any
         } else {
           lds_read_act<Sys::A>(act, slot + tid * Sys::A, 1);
         }
-        // prefetch step k+D into the slot step k-1 used (every reader is past this
-        // point); near the end re-read step K-1: no branch, same op count
-        issue(dsrc, (k + D) % kDmaSlots);
-        if (k + D + 1 < a.K) dsrc += dstride;
+        Ring::refill(dsrc, dstride, k, a.K, m0_wave);
       } else {
-        // a ragged last group / unaligned actions: each lane loads its own row, ONE STEP
-        // AHEAD into registers (a load issued and waited for in the same step put a memory
-        // round trip into every step of the group's chain: PMSM 24,608 x 2048, one ragged
-        // group of 32 envs, 3,421 us against 2,094 at 24,576, profiles/r06/pair/); the
-        // barrier keeps the obs tile's reuse rule of the staged full path
+        // a ragged last group / unaligned actions: each lane's own row, one step ahead
+        // (act_row_ahead); the barrier keeps the obs tile's reuse rule of the staged full path
         wg_barrier<false>();
-        if (live) {
-          if (k == 0) {
-#pragma unroll
-            for (int j = 0; j < Sys::A; ++j) anext[j] = gload<true>(gact + i * Sys::A + j);
-          }
-#pragma unroll
-          for (int j = 0; j < Sys::A; ++j) act[j] = anext[j];
-          if (k + 1 < a.K) {
-#pragma unroll
-            for (int j = 0; j < Sys::A; ++j) anext[j] = gload<true>(gact + (off + a.n + i) * Sys::A + j);
-          }
-        }
+        if (live) act_row_ahead<Sys::A>(act, anext, gact, i, off, a.n, k, a.K);
       }
     }
     T o[Sys::O];
@@ -1067,30 +930,19 @@ __device__ __forceinline__ void split_loop(Sys& sys, int32_t& steps, bool& any_r
   // vector-memory ops every step issues after its DMA (lower bound): reward or done
   // (two exec-masked stores) + at least one obs store
   constexpr int kSt = 3;
-  constexpr int kA = kRow ? 1 : Sys::A;
-  constexpr int kSteady = kSt + (D - 1) * (kA + kSt);
-  static_assert(D >= 1 && kSteady <= 63, "vmcnt immediate (6 bits on gfx9)");
-  constexpr int kDmaSlots = dma_slots<D>();
-  constexpr int kSlotF = kRow ? kRowRegionF : 64 * Sys::A;  // floats per slot
-  const uint32_t m0_wave = __builtin_amdgcn_readfirstlane(lds_off(s_act));
-  auto issue = [&](const float* src, int slot) __attribute__((always_inline)) {
-    if constexpr (kRow) {
-      dma16_nt(src, m0_wave + (uint32_t)(slot * kSlotF) * 4u);
-    } else {
-#pragma unroll
-      for (int j = 0; j < Sys::A; ++j) dma4_nt(src + j, m0_wave + (uint32_t)((slot * Sys::A + j) * 64) * 4u);
-    }
-  };
+  // the action ring (lz_act_ring.h) of a 32-env wave; kRow: lane tid loads chunk tid mod C
+  // of the wave's 32-env slice; else: lane tid loads its own env's components
+  using Ring = ActRing<Sys::A, 32, 64, D, kSt, kRow ? ActLayout::Row : ActLayout::Direct>;
+  const uint32_t m0_wave = Ring::wave_m0(s_act, 0);
   const int64_t dstride = a.n * Sys::A;
-  // kRow: lane tid loads chunk tid mod C of the wave's 32-env slice; else: lane tid
-  // loads its own env's components
-  const int64_t src_el = kRag ? min(el, nb - 1) : el;
-  const int src_chunk = kRag ? min(tid % (32 * Sys::A / 4), nb * Sys::A / 4 - 1) : tid % (32 * Sys::A / 4);
+  const int64_t src_el = Ring::template src_row<kRag>(el, nb);
+  const int src_chunk = Ring::template src_chunk<kRag>(tid, nb);
   const float* dsrc = kRow ? gact + base * Sys::A + 4 * src_chunk : gact + (base + src_el) * Sys::A;
   if constexpr (FULL) __builtin_amdgcn_s_waitcnt(0x0F70);
+  // the prologue fill, written out: Ring::fill() here changes k_rollout_pair<SysPMSM, float, 15>
   if constexpr (FULL && Sys::kUsesAction) {
 #pragma unroll
-    for (int d = 0; d < D; ++d) issue(dsrc + (int64_t)(d < a.K ? d : a.K - 1) * dstride, d);
+    for (int d = 0; d < D; ++d) Ring::issue(dsrc + (int64_t)(d < a.K ? d : a.K - 1) * dstride, m0_wave, d);
     dsrc += (int64_t)(D < a.K ? D : a.K - 1) * dstride;
   }
   float znext[3] = {0.0f, 0.0f, 0.0f};  // kPair: lane 0's normals for the next (odd) step
@@ -1100,18 +952,17 @@ __device__ __forceinline__ void split_loop(Sys& sys, int32_t& steps, bool& any_r
     float act[Sys::A];
     if constexpr (Sys::kUsesAction) {
       if constexpr (FULL) {
-        if constexpr (decltype(ladder)::value) ladder_wait<D, kA, kSt>(k);
-        else wait_vmcnt<kSteady>();
-        const float* slot = s_act + (k % kDmaSlots) * kSlotF;
+        Ring::template wait<decltype(ladder)::value>(k);
+        const float* slot = Ring::slot(s_act, k);
         if constexpr (kRow) {
 #pragma unroll
           for (int j = 0; j < Sys::A; ++j) act[j] = slot[el * Sys::A + j];
         } else {
           lds_read_act<Sys::A>(act, slot + tid, 64);
         }
-        issue(dsrc, (k + D) % kDmaSlots);
-        if (k + D + 1 < a.K) dsrc += dstride;
-      } else if (live) {  // ragged / unaligned: the lane's row, one step ahead (rollout_loop)
+        Ring::refill(dsrc, dstride, k, a.K, m0_wave);
+      } else if (live) {  // ragged / unaligned: the lane's row, one step ahead -- written out:
+        // act_row_ahead() here changes the done-free LORENZ3 k_rollout_split code
         if (k == 0) {
 #pragma unroll
           for (int j = 0; j < Sys::A; ++j) anext[j] = gload<true>(gact + i * Sys::A + j);
@@ -1238,14 +1089,22 @@ static inline int64_t grid_for(int64_t n) { return (n + kBlock - 1) / kBlock; }
 // profiles/r06/pair/).  Variant bit 1<<27 forces it at any N, 1<<28 disables it; the
 // other kernels' force bits (256 / 512 split choice, 1<<23 / 1<<24 group shape, 1<<25
 // producer wave, 1<<26 kZN) select theirs.
+// The systems that instantiate the tuning variants -- the step variants V and the prefetch
+// distances 3 / 15 (A/B tools use LORENZ3 float32 and PMSM; the other systems always run
+// the default variant and ignore those bits)
+template <class Sys>
+constexpr bool has_variants() {
+  return std::is_same<Sys, SysL3<float>>::value || std::is_same<Sys, SysPMSM>::value;
+}
+
 template <class Sys>
 static inline bool rollout_pair(const KArgs& a) {
   if constexpr (!std::is_same<Sys, SysPMSM>::value) {
     return false;
   } else {
-    if (a.variant & (1 << 28)) return false;
-    if (a.variant & (1 << 27)) return true;
-    if (a.variant & (256 | 512 | (1 << 23) | (1 << 24) | (1 << 25) | (1 << 26))) return false;
+    if (a.variant & kVarNoPair) return false;
+    if (a.variant & kVarForcePair) return true;
+    if (a.variant & kVarOtherRollout) return false;
     const int64_t cus = a.num_cus > 0 ? a.num_cus : 256, waves = (a.n + 31) / 32;
     return waves > 2 * cus && waves <= 4 * cus;
   }
@@ -1254,42 +1113,41 @@ static inline bool rollout_pair(const KArgs& a) {
 template <class Sys>
 static inline bool rollout_split(const KArgs& a) {
   if constexpr (Sys::O % 2 != 0) return false;
-  if (a.variant & 256) return false;
-  if (a.variant & 512) return true;
+  if (a.variant & kVarOneLane) return false;
+  if (a.variant & kVarTwoLanes) return true;
   return std::is_same<Sys, SysL3<float>>::value && a.n >= 32768;
 }
 
-// Which rollout kernel launch_rollout_d picks (lz_get_launch_shape reports it): 0 the
-// 256-lane k_rollout, 1 one-wave k_rollout, 2 the split-lane kernel; no_done = the
-// done-free instantiation.
+// Which rollout kernel a launch runs, every selector decided ONCE here (rollout_plan):
+// launch_rollout_d maps the plan to an instantiation and lz_get_launch_shape reports it
+// (env_shape_t), so the two cannot disagree.
+enum class RolloutKind { Block, Wave, Split, Pair };  // 256-lane, one-wave, split lanes, lane pair (PMSM)
 struct RolloutPlan {
-  int kind;  // 0 256-lane, 1 one-wave, 2 split lanes, 3 lane pair (PMSM)
-  bool no_done;
-  bool np;  // one-wave groups with a noise-producer wave (k_rollout kNP)
+  RolloutKind kind;
+  bool no_done;  // Block, Split: the done-free instantiation (kNoDone)
+  bool np;       // Wave: one-wave groups with a noise-producer wave (k_rollout_np)
+  bool zn;       // Block, Wave: the next step's normals drawn during this step (kZN)
+  bool done_t;   // Block: temporal done-byte stores (kDoneT; the other kernels' policy is fixed)
+  int sv;        // Split, done-free: the store policy SV (1 = the default)
+  int dist;      // prefetch distance: D of Block / Wave, DS of Split / Pair
+  bool halves() const { return kind == RolloutKind::Split || kind == RolloutKind::Pair; }
+  int envs_per_wave() const { return halves() ? 32 : 64; }
+  int waves() const { return kind == RolloutKind::Block ? kBlock / 64 : np ? 2 : 1; }
+  unsigned grid(int64_t n) const {
+    const int64_t per = kind == RolloutKind::Block ? kBlock : envs_per_wave();
+    return (unsigned)((n + per - 1) / per);
+  }
 };
 template <class Sys>
-static RolloutPlan rollout_plan(const KArgs& a) {
-  const int64_t cus = a.num_cus > 0 ? a.num_cus : 256;
-  const int64_t one_wave_below =
-      std::is_same<Sys, SysL3<float>>::value   ? (int64_t)kBlock * cus
-      : std::is_same<Sys, SysL4<float>>::value ? (int64_t)kBlock * cus * 3 / 4
-                                               : 2 * 256 * (int64_t)kBlock;
-  bool nd = false;
-  if constexpr (never_terminates<Sys>::value && !Sys::kNoise) nd = no_done<Sys>(a) && !(a.variant & 2048);
-  if (rollout_pair<Sys>(a)) return {3, false, false};
-  if ((a.n < one_wave_below || (a.variant & (1 << 24))) && !(a.variant & (1 << 23))) {
-    if (rollout_split<Sys>(a)) return {2, nd, false};
-    // variant bit 1<<25: with a noise-producer wave (k_rollout_np; A/B, measured slower:
-    // HR f32 32,768 x 2048 1,840 -> 2,610 us, 65,536 1,823 -> 3,175; PMSM 2,190 -> 2,274 /
-    // 2,111 -> 2,191, profiles/r04/np/)
-    const bool np = Sys::kNoise && Sys::kUsesAction && (a.flags & LZ_FLAG_ADD_NOISE) && (a.variant & (1 << 25));
-    return {1, false, np};
-  }
-  return {0, nd, false};
+constexpr bool rollout_noisy() {  // systems with k_rollout_np and kZN instantiations
+  return Sys::kNoise && Sys::kUsesAction;
 }
-
-template <class Sys, typename T, int D, int DS = D>  // DS: the split-lane kernel's distance
-static void launch_rollout_d(const KArgs& a, hipStream_t s) {
+template <class Sys>
+constexpr bool rollout_done_free() {  // systems with kNoDone instantiations
+  return never_terminates<Sys>::value && !Sys::kNoise;
+}
+template <class Sys>
+static RolloutPlan rollout_plan(const KArgs& a) {
   // fewer 256-env workgroups than CUs: one-wave groups (variant bit 1<<23: the 256-lane
   // kernel at any N, A/B).  At 65,536 envs on 256 CUs the 256-lane kernel (one wave per
   // SIMD, 64 envs each) beats the split-lane one (two per SIMD, 32 envs each, every step
@@ -1301,75 +1159,119 @@ static void launch_rollout_d(const KArgs& a, hipStream_t s) {
   // at 32,768-98,304 (2,209 vs 2,493 / 1,823 vs 2,038 us at 65,536): the round-2 bound.
   // LORENZ4's crossover lies lower, between 160 and 192 workgroups per 256 CUs (40,960
   // envs: 658 vs 918 us; 49,152: 870 vs 925-1,096; 57,344: 908 vs 1,007): from 3/4 x 256 x CUs.
-  // (rollout_plan: variant bit 1<<24 forces one-wave groups at any N, 1<<23 the 256-lane
+  // (variant bit 1<<24 forces one-wave groups at any N, 1<<23 the 256-lane
   // kernel, 2048 keeps the done path -- A/B)
-  const RolloutPlan plan = rollout_plan<Sys>(a);
-  if constexpr (std::is_same<Sys, SysPMSM>::value) {
-    if (plan.kind == 3) {
-      hipLaunchKernelGGL((k_rollout_pair<Sys, T, DS>), dim3((unsigned)((a.n + 31) / 32)), dim3(64), 0, s, a);
-      return;
-    }
+  const int64_t cus = a.num_cus > 0 ? a.num_cus : 256;
+  const int64_t one_wave_below =
+      std::is_same<Sys, SysL3<float>>::value   ? (int64_t)kBlock * cus
+      : std::is_same<Sys, SysL4<float>>::value ? (int64_t)kBlock * cus * 3 / 4
+                                               : 2 * 256 * (int64_t)kBlock;
+  bool nd = false;
+  if constexpr (rollout_done_free<Sys>()) nd = no_done<Sys>(a) && !(a.variant & kVarKeepDone);
+  int d = kDmaDist, ds = kDmaDist;  // ds: the two-lanes-per-env kernels' distance
+  if constexpr (has_variants<Sys>()) {
+    if (a.variant & kVarDist3) d = ds = 3;  // A/B: prefetch distance 3
+    // A/B: split-lane distance 15 (vmcnt allows 59 ops in flight): no change at 32,768 -
+    // 131,071 envs (profiles/r03/rollout/ab_split_dma_distance_15_rejected.json)
+    else if (a.variant & kVarSplitDist15) ds = 15;
   }
-  if (plan.kind != 0) {
-    if (plan.kind == 2) {
-      const dim3 g((unsigned)((a.n + 31) / 32));
-      if constexpr (never_terminates<Sys>::value && !Sys::kNoise) {
-        if (plan.no_done) {
-          switch ((a.variant >> 18) & 7) {  // A/B: store policy (SV; 1 = the default)
-            case 1: hipLaunchKernelGGL((k_rollout_split<Sys, T, 2, DS, true, 0>), g, dim3(64), 0, s, a); return;
-            case 3: hipLaunchKernelGGL((k_rollout_split<Sys, T, 2, DS, true, 3>), g, dim3(64), 0, s, a); return;
-            case 4: hipLaunchKernelGGL((k_rollout_split<Sys, T, 2, DS, true, 5>), g, dim3(64), 0, s, a); return;
-            case 7: hipLaunchKernelGGL((k_rollout_split<Sys, T, 2, DS, true, 7>), g, dim3(64), 0, s, a); return;
-            default: break;
-          }
-          hipLaunchKernelGGL((k_rollout_split<Sys, T, 2, DS, true>), g, dim3(64), 0, s, a);
-          return;
+  RolloutPlan p = {RolloutKind::Block, false, false, false, true, 1, d};
+  if (rollout_pair<Sys>(a)) {
+    p.kind = RolloutKind::Pair;
+    p.dist = ds;
+    return p;
+  }
+  if ((a.n < one_wave_below || (a.variant & kVarForceWave)) && !(a.variant & kVarForceBlock)) {
+    if (rollout_split<Sys>(a)) {
+      p.kind = RolloutKind::Split;
+      p.no_done = nd;
+      p.dist = ds;
+      if (nd) {
+        switch ((a.variant >> kVarSplitSvShift) & kVarSplitSvMask) {  // A/B: store policy (SV; 1 = the default)
+          case 1: p.sv = 0; break;
+          case 3: p.sv = 3; break;
+          case 4: p.sv = 5; break;
+          case 7: p.sv = 7; break;
+          default: break;
         }
       }
-      hipLaunchKernelGGL((k_rollout_split<Sys, T, 2, DS>), g, dim3(64), 0, s, a);
-    } else if constexpr (Sys::kNoise && Sys::kUsesAction) {
-      if (plan.np)
-        hipLaunchKernelGGL((k_rollout_np<Sys, T, D>), dim3((unsigned)((a.n + 63) / 64)), dim3(128), 0, s, a);
-      else if (a.variant & (1 << 26))  // A/B: the next step's normals drawn during this step (kZN)
-        hipLaunchKernelGGL((k_rollout<Sys, T, 64, D, false, true, true>), dim3((unsigned)((a.n + 63) / 64)),
-                           dim3(64), 0, s, a);
-      else
-        hipLaunchKernelGGL((k_rollout<Sys, T, 64, D>), dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a);
-    } else {
-      hipLaunchKernelGGL((k_rollout<Sys, T, 64, D>), dim3((unsigned)((a.n + 63) / 64)), dim3(64),
-                         0, s, a);
+      return p;
     }
-  } else {
-    if constexpr (never_terminates<Sys>::value && !Sys::kNoise) {
-      if (plan.no_done) {
-        if (a.variant & (1 << 21))  // A/B: non-temporal done stores
-          hipLaunchKernelGGL((k_rollout<Sys, T, kBlock, D, true, false>), dim3((unsigned)grid_for(a.n)),
-                             dim3(kBlock), 0, s, a);
-        else
-          hipLaunchKernelGGL((k_rollout<Sys, T, kBlock, D, true>), dim3((unsigned)grid_for(a.n)),
-                             dim3(kBlock), 0, s, a);
-        return;
-      }
-    }
-    if constexpr (Sys::kNoise && Sys::kUsesAction) {
-      if (a.variant & (1 << 26)) {  // A/B: kZN, as above
-        hipLaunchKernelGGL((k_rollout<Sys, T, kBlock, D, false, true, true>), dim3((unsigned)grid_for(a.n)),
-                           dim3(kBlock), 0, s, a);
-        return;
-      }
-    }
-    if (a.variant & (1 << 21))  // A/B: non-temporal done stores
-      hipLaunchKernelGGL((k_rollout<Sys, T, kBlock, D, false, false>), dim3((unsigned)grid_for(a.n)),
-                         dim3(kBlock), 0, s, a);
-    else
-      hipLaunchKernelGGL((k_rollout<Sys, T, kBlock, D>), dim3((unsigned)grid_for(a.n)), dim3(kBlock),
-                         0, s, a);
+    p.kind = RolloutKind::Wave;
+    // variant bit 1<<25: with a noise-producer wave (k_rollout_np; A/B, measured slower:
+    // HR f32 32,768 x 2048 1,840 -> 2,610 us, 65,536 1,823 -> 3,175; PMSM 2,190 -> 2,274 /
+    // 2,111 -> 2,191, profiles/r04/np/)
+    p.np = rollout_noisy<Sys>() && (a.flags & LZ_FLAG_ADD_NOISE) && (a.variant & kVarProducer);
+    p.zn = rollout_noisy<Sys>() && !p.np && (a.variant & kVarZN);  // A/B: kZN
+    return p;
   }
+  p.no_done = nd;
+  p.zn = rollout_noisy<Sys>() && (a.variant & kVarZN);  // A/B: kZN (a noisy system is never done-free)
+  p.done_t = p.zn || !(a.variant & kVarDoneNT);         // A/B: non-temporal done stores
+  return p;
 }
 
-// kVariants: instantiate the step-kernel tuning variants (A/B tools use LORENZ3 and
-// PMSM; the other systems always run the default variant)
-template <class Sys, typename T, bool kVariants = false>
+// The plan's instantiation, one flat mapping per kernel layout.  `if constexpr` only keeps
+// a system from instantiating kernels it has none of; the plan never selects those.
+#define LZ_GO(...)                                             \
+  do {                                                         \
+    hipLaunchKernelGGL((__VA_ARGS__), g, b, 0, s, a);          \
+    return;                                                    \
+  } while (0)
+template <class Sys, typename T, int D>  // one env per lane: RolloutKind::Block / Wave
+static void launch_rollout_lanes(const RolloutPlan& p, const KArgs& a, hipStream_t s) {
+  const dim3 g(p.grid(a.n)), b(64u * p.waves());
+  if (p.kind == RolloutKind::Wave) {
+    if constexpr (rollout_noisy<Sys>()) {
+      if (p.np) LZ_GO(k_rollout_np<Sys, T, D>);
+      if (p.zn) LZ_GO(k_rollout<Sys, T, 64, D, false, true, true>);
+    }
+    LZ_GO(k_rollout<Sys, T, 64, D>);
+  }
+  if constexpr (rollout_done_free<Sys>()) {
+    if (p.no_done && p.done_t) LZ_GO(k_rollout<Sys, T, kBlock, D, true>);
+    if (p.no_done) LZ_GO(k_rollout<Sys, T, kBlock, D, true, false>);
+  }
+  if constexpr (rollout_noisy<Sys>()) {
+    if (p.zn) LZ_GO(k_rollout<Sys, T, kBlock, D, false, true, true>);
+  }
+  if (p.done_t) LZ_GO(k_rollout<Sys, T, kBlock, D>);
+  LZ_GO(k_rollout<Sys, T, kBlock, D, false, false>);
+}
+template <class Sys, typename T, int DS>  // two lanes per env: RolloutKind::Split / Pair
+static void launch_rollout_halves(const RolloutPlan& p, const KArgs& a, hipStream_t s) {
+  const dim3 g(p.grid(a.n)), b(64);
+  if constexpr (std::is_same<Sys, SysPMSM>::value) {
+    if (p.kind == RolloutKind::Pair) LZ_GO(k_rollout_pair<Sys, T, DS>);
+  }
+  if constexpr (rollout_done_free<Sys>()) {
+    if (p.no_done) {
+      switch (p.sv) {
+        case 0: LZ_GO(k_rollout_split<Sys, T, 2, DS, true, 0>);
+        case 3: LZ_GO(k_rollout_split<Sys, T, 2, DS, true, 3>);
+        case 5: LZ_GO(k_rollout_split<Sys, T, 2, DS, true, 5>);
+        case 7: LZ_GO(k_rollout_split<Sys, T, 2, DS, true, 7>);
+        default: LZ_GO(k_rollout_split<Sys, T, 2, DS, true>);
+      }
+    }
+  }
+  LZ_GO(k_rollout_split<Sys, T, 2, DS>);
+}
+#undef LZ_GO
+
+template <class Sys, typename T>
+static void launch_rollout_d(const KArgs& a, hipStream_t s) {
+  const RolloutPlan p = rollout_plan<Sys>(a);
+  if constexpr (has_variants<Sys>()) {  // the only systems with other distances than kDmaDist
+    if (p.dist == 3 && p.halves()) return launch_rollout_halves<Sys, T, 3>(p, a, s);
+    if (p.dist == 3) return launch_rollout_lanes<Sys, T, 3>(p, a, s);
+    if (p.dist == 15) return launch_rollout_halves<Sys, T, 15>(p, a, s);  // (rollout_plan: halves only)
+  }
+  if (p.halves()) return launch_rollout_halves<Sys, T, kDmaDist>(p, a, s);
+  launch_rollout_lanes<Sys, T, kDmaDist>(p, a, s);
+}
+
+template <class Sys, typename T>
 static int launch_all(EnvLaunch which, const KArgs& a, hipStream_t s) {
   const dim3 grid((unsigned)grid_for(a.n)), block(kBlock);
   const int tiles = which == EnvLaunch::Step && multi_step_ok<Sys>::value ? step_tiles<Sys>(a) : 1;
@@ -1380,33 +1282,31 @@ static int launch_all(EnvLaunch which, const KArgs& a, hipStream_t s) {
       const int64_t per = (int64_t)kBlock * tiles;
       const dim3 g((unsigned)((a.n + per - 1) / per));
       if (tiles == 2) hipLaunchKernelGGL((k_step_multi<Sys, T, 2>), g, block, 0, s, a);
-      else if (a.variant & (1 << 22))  // A/B: temporal done stores
+      else if (a.variant & kVarMultiDoneT)  // A/B: temporal done stores
         hipLaunchKernelGGL((k_step_multi<Sys, T, 4, true>), g, block, 0, s, a);
       else hipLaunchKernelGGL((k_step_multi<Sys, T, 4>), g, block, 0, s, a);
     }
-  } else if (which == EnvLaunch::Step && !kVariants) {
+  } else if (which == EnvLaunch::Step && !has_variants<Sys>()) {
     hipLaunchKernelGGL((k_step<Sys, T, 0>), grid, block, 0, s, a);
   } else if (which == EnvLaunch::Step) {
-    switch (a.variant & 63) {
+    {  // (instantiated for every system, run by has_variants: the set of built kernels is pinned)
+      switch (a.variant & kVarStepMask) {
 #define LZ_STEP_V(VV)                                                                   \
   case VV:                                                                              \
     hipLaunchKernelGGL((k_step<Sys, T, VV>),                                            \
                        dim3((unsigned)((a.n + step_block<VV>() - 1) / step_block<VV>())), \
                        dim3(step_block<VV>()), 0, s, a);                                \
     break;
-      LZ_STEP_V(1) LZ_STEP_V(2) LZ_STEP_V(3) LZ_STEP_V(4) LZ_STEP_V(5)
-      LZ_STEP_V(8) LZ_STEP_V(16) LZ_STEP_V(24) LZ_STEP_V(32)
+        LZ_STEP_V(kVarStepPlain) LZ_STEP_V(kVarStepDirect) LZ_STEP_V(kVarStepPlain | kVarStepDirect)
+        LZ_STEP_V(kVarStepFullBar) LZ_STEP_V(kVarStepPlain | kVarStepFullBar)
+        LZ_STEP_V(kVarStepBlock512) LZ_STEP_V(kVarStepBlock128) LZ_STEP_V(kVarStepBlock1024)
+        LZ_STEP_V(kVarStepDoneT)
 #undef LZ_STEP_V
-      default: hipLaunchKernelGGL((k_step<Sys, T, 0>), grid, block, 0, s, a); break;
+        default: hipLaunchKernelGGL((k_step<Sys, T, 0>), grid, block, 0, s, a); break;
+      }
     }
-  } else if constexpr (kVariants) {
-    if (a.variant & 1024) launch_rollout_d<Sys, T, 3>(a, s);  // A/B: prefetch distance 3
-    // A/B: split-lane distance 15 (vmcnt allows 59 ops in flight): no change at 32,768 -
-    // 131,071 envs (profiles/r03/rollout/ab_split_dma_distance_15_rejected.json)
-    else if (a.variant & 4096) launch_rollout_d<Sys, T, kDmaDist, 15>(a, s);
-    else launch_rollout_d<Sys, T, kDmaDist>(a, s);
   } else {
-    launch_rollout_d<Sys, T, kDmaDist>(a, s);
+    launch_rollout_d<Sys, T>(a, s);
   }
   return (int)hipGetLastError();
 }
@@ -1414,16 +1314,14 @@ static int launch_all(EnvLaunch which, const KArgs& a, hipStream_t s) {
 static int dispatch(EnvLaunch which, int system, int f64, const KArgs& a, void* stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   return for_system(system, f64 != 0, [&](auto tag) {
-    using Sys = typename decltype(tag)::Sys;
-    constexpr bool kVariants = std::is_same<Sys, SysL3<float>>::value || std::is_same<Sys, SysPMSM>::value;
-    return launch_all<Sys, typename decltype(tag)::T, kVariants>(which, a, s);
+    return launch_all<typename decltype(tag)::Sys, typename decltype(tag)::T>(which, a, s);
   });
 }
 
 // ------------------------------------------------------------------ launch shapes
 // What lz_step / lz_rollout launch for these arguments (lz_get_launch_shape): kernel code,
 // envs per wave, waves per workgroup, workgroups, flags (lorenz_env.h LZ_KERNEL_* /
-// LZ_SHAPE_*) -- the same decisions launch_all / launch_rollout_d take.
+// LZ_SHAPE_*) -- the same decisions launch_all takes, the rollout's from the same plan.
 template <class Sys, typename T>
 static int env_shape_t(EnvLaunch which, const KArgs& a, EnvShape& o) {
   if (which == EnvLaunch::Step) {
@@ -1437,14 +1335,13 @@ static int env_shape_t(EnvLaunch which, const KArgs& a, EnvShape& o) {
     return 0;
   }
   const RolloutPlan p = rollout_plan<Sys>(a);
-  o.kernel = p.kind == 0   ? LZ_KERNEL_ROLLOUT
-             : p.kind == 1 ? LZ_KERNEL_ROLLOUT_WAVE
-             : p.kind == 2 ? LZ_KERNEL_ROLLOUT_SPLIT
-                           : LZ_KERNEL_ROLLOUT_PAIR;
-  o.envs_per_wave = p.kind >= 2 ? 32 : 64;
-  o.waves = p.kind == 0 ? kBlock / 64 : p.np ? 2 : 1;
-  const int64_t per = p.kind == 0 ? kBlock : p.kind == 1 ? 64 : 32;
-  o.grid = (int32_t)((a.n + per - 1) / per);
+  o.kernel = p.kind == RolloutKind::Block   ? LZ_KERNEL_ROLLOUT
+             : p.kind == RolloutKind::Wave  ? LZ_KERNEL_ROLLOUT_WAVE
+             : p.kind == RolloutKind::Split ? LZ_KERNEL_ROLLOUT_SPLIT
+                                            : LZ_KERNEL_ROLLOUT_PAIR;
+  o.envs_per_wave = p.envs_per_wave();
+  o.waves = p.waves();
+  o.grid = (int32_t)p.grid(a.n);
   o.flags = p.no_done ? LZ_SHAPE_NO_DONE : 0;
   return 0;
 }
@@ -1769,9 +1666,9 @@ static int launch_vn(const KArgs& a, const VArgs& v, hipStream_t s) {
   const int vb = vn_block(a.n);
   const unsigned grid = (unsigned)((a.n + vb - 1) / vb);
   if (vb == 1024)
-    hipLaunchKernelGGL((k_step_vn<Sys, T, 24>), dim3(grid), dim3(1024), 0, s, a, v);
+    hipLaunchKernelGGL((k_step_vn<Sys, T, kVarStepBlock1024>), dim3(grid), dim3(1024), 0, s, a, v);
   else if (vb == 512)
-    hipLaunchKernelGGL((k_step_vn<Sys, T, 8>), dim3(grid), dim3(512), 0, s, a, v);
+    hipLaunchKernelGGL((k_step_vn<Sys, T, kVarStepBlock512>), dim3(grid), dim3(512), 0, s, a, v);
   else
     hipLaunchKernelGGL((k_step_vn<Sys, T, 0>), dim3(grid), dim3(256), 0, s, a, v);
   if ((v.flags & LZ_VN_DEFER) || ((v.flags & LZ_VN_TRAINING) && !v.fused))

@@ -2861,7 +2861,7 @@ PolShape f32_policy_shape(int64_t n, int num_cus, int variant) {
     return w == 4 || w == 8 ? w : 0;
   }();
   PolShape s = {32, forced ? forced : tiles >= 8 * (int64_t)num_cus ? 8 : 4, 0, 0};
-  if (!forced && s.waves == 4 && !(variant & 8192)) s.pair = 1;
+  if (!forced && s.waves == 4 && !(variant & kVarPolF32OneWave)) s.pair = 1;
   const int64_t groups = (tiles + s.waves - 1) / s.waves;
   s.grid = (int)(groups < num_cus ? groups : num_cus);
   return s;

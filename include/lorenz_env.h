@@ -230,7 +230,7 @@ typedef struct lz_config {
    * replays the accumulator; the step index where it fires (-1 = never, which is the
    * case for the reference constants) is stored here by lz_create. Read-only. */
   int32_t t_done_step;
-  int32_t reserved[6];       /* reserved[0]: kernel tuning variant (A/B experiments) */
+  int32_t reserved[6];       /* reserved[0]: kernel tuning variant (A/B experiments; bit table: DESIGN.md 4.2.1) */
   int32_t integrator;        /* lz_integrator (LZ_INT_EULER = the reference, default) */
 } lz_config;
 
