@@ -1159,7 +1159,15 @@ const PolicyRow kPolicyTable[] = {  // indexed by PolicyKind
     {lz::PolicyKind::EvalF32AttnLn, LZ_CALL_EVALUATE_POLICY_ATTN_STACK_F32, LZ_KERNEL_EVAL_ATTN_F32,
      lz::eval_attn_f32_policy_shape, true, false,
      "the fused frame-stacked evaluation runs LORENZ3 / PMSM / HR"},
+    {lz::PolicyKind::F32MlpStack, LZ_CALL_ROLLOUT_POLICY_STACK_F32, LZ_KERNEL_POLICY_STACK_F32,
+     lz::stack_f32_policy_shape, true, false, "the frame-stacked rollout runs LORENZ3 / PMSM / HR"},
+    {lz::PolicyKind::EvalF32MlpStack, LZ_CALL_EVALUATE_POLICY_STACK_F32, LZ_KERNEL_EVAL_STACK_F32,
+     lz::stack_f32_policy_shape, true, false, "the fused frame-stacked evaluation runs LORENZ3 / PMSM / HR"},
 };
+// the frame-stacked MlpPolicy's entry points take the reference's n_stack alone
+static bool mlp_stack_kind(lz::PolicyKind k) {
+  return k == lz::PolicyKind::F32MlpStack || k == lz::PolicyKind::EvalF32MlpStack;
+}
 static const PolicyRow& policy_row(lz::PolicyKind k) { return kPolicyTable[(int)k]; }
 static lz::PolShape policy_shape_of(const lz_handle* h, const PolicyRow& row) {
   return row.shape(h->cfg.num_envs, h->num_cus, h->cfg.reserved[0]);
@@ -1221,6 +1229,7 @@ static lz_status rollout_policy(lz_handle* h, const lz_policy_rollout_args* r, l
   RESIDENT_QUIESCE(h);
   const PolicyRow& row = policy_row(kind);
   if (row.stacked) {
+    if (mlp_stack_kind(kind) && n_stack != 4) return fail(LZ_ERR_UNSUPPORTED, "n_stack must be 4");
     if (n_stack != 1 && n_stack != 4) return fail(LZ_ERR_UNSUPPORTED, "n_stack must be 1 or 4");
     if (!stack_in || !stack_out) return fail(LZ_ERR_INVALID, "stack_in / stack_out must be non-NULL");
     if (r->obs_norm || r->obs_moments)
@@ -1392,6 +1401,11 @@ lz_status lz_rollout_policy_attn_stack_f32(lz_handle* h, const lz_policy_rollout
   return rollout_policy(h, r, lz::PolicyKind::F32AttnLn, n_stack, stack_in, stack_out);
 }
 
+lz_status lz_stack_rollout_policy_f32(lz_handle* h, const lz_policy_rollout_args* r, int32_t n_stack,
+                                      const float* stack_in, float* stack_out) {
+  return rollout_policy(h, r, lz::PolicyKind::F32MlpStack, n_stack, stack_in, stack_out);
+}
+
 // ---- fused policy evaluation (lorenz_env.h LZ_EVAL_*; lz_internal.h EArgs)
 // T of a trace (lorenz_env.h lz_eval_trace), or -1 for a start / every it refuses
 static int64_t trace_rows(int32_t K, int32_t start, int32_t every) {
@@ -1434,6 +1448,7 @@ static lz_status evaluate_policy(lz_handle* h, const lz_policy_eval_args* e, lz:
     return fail(LZ_ERR_UNSUPPORTED, "the fused evaluation runs the reference's Euler integrator only");
   if (!(h->desc->policies & lz::pol_bit(kind))) return fail(LZ_ERR_UNSUPPORTED, "%s", row.refusal);
   if (row.stacked) {
+    if (mlp_stack_kind(kind) && n_stack != 4) return fail(LZ_ERR_UNSUPPORTED, "n_stack must be 4");
     if (n_stack != 1 && n_stack != 4) return fail(LZ_ERR_UNSUPPORTED, "n_stack must be 1 or 4");
     if (n_stack * h->desc->obs_dim > lz::kLnMaxIn) return fail(LZ_ERR_UNSUPPORTED, "stacked obs > 32 dims");
     if (e->obs_norm)
@@ -1517,6 +1532,11 @@ lz_status lz_evaluate_policy_attn_f32(lz_handle* h, const lz_policy_eval_args* e
 lz_status lz_evaluate_policy_attn_stack_f32(lz_handle* h, const lz_policy_eval_args* e, int32_t n_stack,
                                             const float* stack_in, float* stack_out) {
   return evaluate_policy(h, e, lz::PolicyKind::EvalF32AttnLn, n_stack, stack_in, stack_out);
+}
+
+lz_status lz_stack_evaluate_policy_f32(lz_handle* h, const lz_policy_eval_args* e, int32_t n_stack,
+                                       const float* stack_in, float* stack_out) {
+  return evaluate_policy(h, e, lz::PolicyKind::EvalF32MlpStack, n_stack, stack_in, stack_out);
 }
 
 lz_status lz_evaluate_policy_f32_trace(lz_handle* h, const lz_policy_eval_args* e, const lz_eval_trace* tr) {

@@ -41,12 +41,12 @@ using SysPMSMf = SysPMSM;  // float32 only: the reference computes it in float32
 template <class Fn>
 inline int for_system(int system, bool f64, Fn&& fn) {
   switch (system) {
-    case LZ_SYS_LORENZ3: return visit_system<SysL3, true, kPolAll | kPolMlpI8 | kPolEval | kPolEvalAttn>(f64, fn);
+    case LZ_SYS_LORENZ3: return visit_system<SysL3, true, kPolAll | kPolMlpI8 | kPolEval | kPolEvalAttn | kPolMlpStack>(f64, fn);
     case LZ_SYS_LORENZ4: return visit_system<SysL4, true, kPolBasic | kPolMlpI8 | kPolEval>(f64, fn);
     case LZ_SYS_LORENZ3 + kSysRK4: return visit_system<SysL3RK4, true, 0u>(f64, fn);
     case LZ_SYS_LORENZ4 + kSysRK4: return visit_system<SysL4RK4, true, 0u>(f64, fn);
-    case LZ_SYS_PMSM: return visit_system<SysPMSMf, false, kPolAll | kPolMlpI8 | kPolEval | kPolEvalAttn>(f64, fn);
-    case LZ_SYS_HR: return visit_system<SysHR, true, kPolAll | kPolMlpI8 | kPolEval | kPolEvalAttn>(f64, fn);
+    case LZ_SYS_PMSM: return visit_system<SysPMSMf, false, kPolAll | kPolMlpI8 | kPolEval | kPolEvalAttn | kPolMlpStack>(f64, fn);
+    case LZ_SYS_HR: return visit_system<SysHR, true, kPolAll | kPolMlpI8 | kPolEval | kPolEvalAttn | kPolMlpStack>(f64, fn);
     case LZ_SYS_T1: return visit_system<SysT1, true, kPolBasic>(f64, fn);
     case LZ_SYS_T2: return visit_system<SysT2, true, kPolBasic>(f64, fn);
     case LZ_SYS_TP: return visit_system<SysTP, true, kPolBasic>(f64, fn);

@@ -6,6 +6,10 @@
 //   LZ_GRAD_KERNEL  the kernel's name
 //   kTail           doubles after the P gradient sums in a workgroup's slot
 //   kLaneSums       float64 per-lane loss sums that go through the lane-order reduction
+//   LZ_GRAD_MAXO    (optional, default 8) the widest input: 24 for k_ppo_grad_h64_wide, the
+//                   frame-stacked MlpPolicy (code/lorenz_filter/train.py:109-131); every
+//                   constant that depends on it is kMO / kW1Ld below, and with the default
+//                   they are the numbers the text had before
 // One text, so the two forms cannot drift apart -- and the preprocessor, not a template
 // parameter, picks the form: each kernel keeps its name and its machine code (measurements
 // are tied to kernel code hashes, tools/kernel_hash.py; DESIGN.md 4.6).  The forms differ in
@@ -50,6 +54,13 @@
 #if LZ_GRAD_H != 128 && LZ_GRAD_H != 64
 #error "lz_grad_body.inc: LZ_GRAD_H must be 128 or 64"
 #endif
+#ifndef LZ_GRAD_MAXO
+#define LZ_GRAD_MAXO 8
+#define LZ_GRAD_MAXO_DEFAULTED 1
+#endif
+#if LZ_GRAD_MAXO % 2 != 0 || (32 * LZ_GRAD_MAXO) % (2 * LZ_GRAD_H) != 0
+#error "lz_grad_body.inc: LZ_GRAD_MAXO must be even and fill whole passes of the x image"
+#endif
 
 __global__ __launch_bounds__(2 * LZ_GRAD_H) void LZ_GRAD_KERNEL(GradArgs a) {
   constexpr int kH = LZ_GRAD_H;         // hidden units (hides grad::kH)
@@ -57,11 +68,15 @@ __global__ __launch_bounds__(2 * LZ_GRAD_H) void LZ_GRAD_KERNEL(GradArgs a) {
   constexpr int kW2Ld = kH + 1;         // row stride of the W2 image
   constexpr int kWaves = kH / 32;       // wave w owns units 32 w .. 32 w + 31
   constexpr int kThreads = 2 * kH;      // = 64 kWaves
+  constexpr int kMO = LZ_GRAD_MAXO;     // widest input (the x and W1 images, accS)
+  // row stride of the W1 image: 8 as it always was; the wide form an odd one as W2's (24
+  // words would put the 32 rows of a column read on 8 banks)
+  constexpr int kW1Ld = kMO == 8 ? 8 : kMO + 1;
   __shared__ float sW2[kH * kW2Ld];
-  __shared__ float sW1[kH * kMaxO];
+  __shared__ float sW1[kH * kW1Ld];
   __shared__ float sB1[kH], sB2[kH];
   __shared__ float sWh[kMaxA * kH];
-  __shared__ float sX[kMaxO * kTile];
+  __shared__ float sX[kMO * kTile];
   __shared__ float sH1[kH * kLd], sH2[kH * kLd], sD2[kH * kLd], sD1[kH * kLd];
   __shared__ float sHP[kWaves * kMaxA * kTile];
   __shared__ float sDO[kMaxA * kTile];
@@ -92,9 +107,9 @@ __global__ __launch_bounds__(2 * LZ_GRAD_H) void LZ_GRAD_KERNEL(GradArgs a) {
   const float* gLs = a.params + oLs;
 
   for (int e = tid; e < kH * kH; e += kThreads) sW2[(e >> kLogH) * kW2Ld + (e & (kH - 1))] = gW2[e];
-  for (int e = tid; e < kH * kMaxO; e += kThreads) {
-    const int u = e >> 3, k = e & 7;
-    sW1[e] = k < O ? gW1[u * O + k] : 0.0f;
+  for (int e = tid; e < kH * kMO; e += kThreads) {
+    const int u = kMO == 8 ? e >> 3 : e / kMO, k = kMO == 8 ? e & 7 : e % kMO;
+    sW1[kMO == 8 ? e : u * kW1Ld + k] = k < O ? gW1[u * O + k] : 0.0f;
   }
   for (int e = tid; e < kH; e += kThreads) {
     sB1[e] = gB1[e];
@@ -123,9 +138,9 @@ __global__ __launch_bounds__(2 * LZ_GRAD_H) void LZ_GRAD_KERNEL(GradArgs a) {
   for (int t = 0; t < kWaves; ++t)
 #pragma unroll
     for (int g = 0; g < 16; ++g) accW2[t][g] = 0.0f;
-  float accS[9];
+  float accS[kMO + 1];
 #pragma unroll
-  for (int i = 0; i < 9; ++i) accS[i] = 0.0f;
+  for (int i = 0; i < kMO + 1; ++i) accS[i] = 0.0f;
 #if LZ_GRAD_PPO
   double lossS = 0.0, entS = 0.0, klS = 0.0, cntS = 0.0, clipS = 0.0, dbh[kMaxA], dls[kMaxA];
 #else
@@ -152,18 +167,18 @@ __global__ __launch_bounds__(2 * LZ_GRAD_H) void LZ_GRAD_KERNEL(GradArgs a) {
       }
     if (tid < kH) {
 #pragma unroll
-      for (int o = 0; o < kMaxO; ++o)
+      for (int o = 0; o < kMO; ++o)
         if (o < O) put(slot + oW1 + tid * O + o, accS[o], first);
-      put(slot + oB1 + tid, accS[8], first);
+      put(slot + oB1 + tid, accS[kMO], first);
     } else {
       const int u = tid - kH;
-      put(slot + oB2 + u, accS[8], first);
+      put(slot + oB2 + u, accS[kMO], first);
 #pragma unroll
       for (int j = 0; j < kMaxA; ++j)
         if (j < NH) put(slot + oWh + j * kH + u, accS[j], first);
     }
 #pragma unroll
-    for (int i = 0; i < 9; ++i) accS[i] = 0.0f;
+    for (int i = 0; i < kMO + 1; ++i) accS[i] = 0.0f;
     first = false;
     since = 0;
   };
@@ -182,7 +197,7 @@ __global__ __launch_bounds__(2 * LZ_GRAD_H) void LZ_GRAD_KERNEL(GradArgs a) {
     // x as [k][sample]; rows k >= O and samples that are not read are 0 (kThreads / 32 rows
     // a pass: one pass with 256 threads, two with 128)
 #pragma unroll
-    for (int k0 = 0; k0 < kMaxO; k0 += kThreads / 32) {
+    for (int k0 = 0; k0 < kMO; k0 += kThreads / 32) {
       const int k = k0 + (tid >> 5);
       sX[k * kTile + r] = (k < O && valid) ? a.obs[row * O + k] : 0.0f;
     }
@@ -190,7 +205,7 @@ __global__ __launch_bounds__(2 * LZ_GRAD_H) void LZ_GRAD_KERNEL(GradArgs a) {
     // x as [k][sample]; rows k >= O and samples past the end are 0 (kThreads / 32 rows a
     // pass: one pass with 256 threads, two with 128)
 #pragma unroll
-    for (int k0 = 0; k0 < kMaxO; k0 += kThreads / 32) {
+    for (int k0 = 0; k0 < kMO; k0 += kThreads / 32) {
       const int k = k0 + (tid >> 5), s = tid & 31;
       const int64_t i = base + s;
       sX[k * kTile + s] = (k < O && i < a.n) ? a.obs[i * O + k] : 0.0f;
@@ -205,8 +220,8 @@ __global__ __launch_bounds__(2 * LZ_GRAD_H) void LZ_GRAD_KERNEL(GradArgs a) {
 #pragma unroll
     for (int g = 0; g < 16; ++g) c[g] = sB1[32 * w + acc_row(g, h)];
 #pragma unroll
-    for (int st = 0; st < kMaxO / 2; ++st)
-      c = mfma(sW1[(32 * w + r) * kMaxO + 2 * st + h], sX[(2 * st + h) * kTile + r], c);
+    for (int st = 0; st < kMO / 2; ++st)
+      c = mfma(sW1[(32 * w + r) * kW1Ld + 2 * st + h], sX[(2 * st + h) * kTile + r], c);
 #pragma unroll
     for (int g = 0; g < 16; ++g) {
       h1[g] = tanhf(c[g]);
@@ -399,15 +414,15 @@ __global__ __launch_bounds__(2 * LZ_GRAD_H) void LZ_GRAD_KERNEL(GradArgs a) {
 #pragma unroll 4
       for (int s = 0; s < kTile; ++s) {
         const float d = sD1[tid * kLd + s];
-        accS[8] += d;
+        accS[kMO] += d;
 #pragma unroll
-        for (int o = 0; o < kMaxO; ++o) accS[o] = fmaf(d, sX[o * kTile + s], accS[o]);
+        for (int o = 0; o < kMO; ++o) accS[o] = fmaf(d, sX[o * kTile + s], accS[o]);
       }
     } else {  // db2 and the head rows' column of unit tid - kH
       const int u = tid - kH;
 #pragma unroll 4
       for (int s = 0; s < kTile; ++s) {
-        accS[8] += sD2[u * kLd + s];
+        accS[kMO] += sD2[u * kLd + s];
         const float hv = sH2[u * kLd + s];
 #pragma unroll
         for (int j = 0; j < kMaxA; ++j) accS[j] = fmaf(sDO[j * kTile + s], hv, accS[j]);
@@ -475,3 +490,7 @@ __global__ __launch_bounds__(2 * LZ_GRAD_H) void LZ_GRAD_KERNEL(GradArgs a) {
     }
   }
 }
+#ifdef LZ_GRAD_MAXO_DEFAULTED
+#undef LZ_GRAD_MAXO
+#undef LZ_GRAD_MAXO_DEFAULTED
+#endif

@@ -271,6 +271,31 @@ constexpr int kTanhSegs = 73;
 constexpr int kF32Tanh = kF32LogStd + 64;
 constexpr int kF32BlobBytes = kF32Tanh + kTanhSegs * 32;  // 148448 B (resident in LDS)
 
+// The float32 MlpPolicy on a 4-frame VecFrameStack (code/lorenz_filter/train.py:109-131: SB3's
+// default 64 x 64 Tanh nets on a 24-wide stacked observation), lz_policy_pack_stack_f32 ->
+// k_rollout_policy_stack_f32 / k_evaluate_policy_stack_f32.  A native 64-unit blob, because
+// the kF32* blob with 12 layer-1 k-steps instead of 4 is 148,448 + 2 x 8,192 = 164,832 B,
+// more than a workgroup's 163,840 B of LDS.  Per net, the kF32* layout with 2 out tiles
+// and 12 layer-1 k-steps:
+//   W1 [2 out tiles][64 lanes][12 k-steps] f32 (lane (r, h), k-step s: W1[32t + r][2s + h]),
+//   W2 [2 out tiles][8 quads][64 lanes][4] f32 (k-step q = 4 quad + e: input unit
+//      32 (q >> 4) + row(q & 15, h)), b1 / b2 [2][2 halves][16] f32, head rows
+//   [4][2 halves][32] f32 (element 16t + g: unit 32t + row(g, h)), head bias [4] f32 and
+//   the format tag in the same 64 B; log_std / Normal constants float[16] after both nets,
+//   then the tanh table.
+constexpr int kStkHidden = 64, kStkMaxIn = 24, kStkKS1 = kStkMaxIn / 2;
+constexpr int kStkW1 = 0;
+constexpr int kStkW2 = kStkW1 + 2 * 64 * kStkKS1 * 4;
+constexpr int kStkB1 = kStkW2 + 2 * 8 * 64 * 4 * 4;
+constexpr int kStkB2 = kStkB1 + 2 * 2 * 16 * 4;
+constexpr int kStkH = kStkB2 + 2 * 2 * 16 * 4;
+constexpr int kStkHB = kStkH + 4 * 2 * 32 * 4;
+constexpr int kStkTag = kStkHB + 48;               // net 0 (pi), as kF32Tag
+constexpr int kStkNet = kStkHB + 64;               // 24,128 B
+constexpr int kStkLogStd = 2 * kStkNet;
+constexpr int kStkTanh = kStkLogStd + 64;
+constexpr int kStkBlobBytes = kStkTanh + 73 * 32;  // 50,656 B (resident in LDS)
+
 // The attention actor-critics at SB3's precision (float32 operands and accumulation;
 // lz_attn_policy_pack_f32 / lz_attn_ln_policy_pack_f32 -> k_rollout_policy_attn_f32).
 // Every product-sum runs on v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain: lane group
@@ -483,6 +508,8 @@ enum class PolicyKind {
   EvalF32Mlp,    // lz_evaluate_policy_f32
   EvalF32Attn,   // lz_evaluate_policy_attn_f32
   EvalF32AttnLn, // lz_evaluate_policy_attn_stack_f32
+  F32MlpStack,     // lz_stack_rollout_policy_f32 (64-unit MlpPolicy on a 4-frame VecFrameStack)
+  EvalF32MlpStack, // lz_stack_evaluate_policy_f32
 };
 constexpr unsigned pol_bit(PolicyKind k) { return 1u << (int)k; }
 // which kinds are built for a system (lz_dispatch.h for_system): every system runs the
@@ -500,6 +527,9 @@ constexpr unsigned kPolMlpI8 = 1u << 16;
 // (kPolEvalAttn: LORENZ3 / PMSM / HR)
 constexpr unsigned kPolEval = pol_bit(PolicyKind::EvalF32Mlp);
 constexpr unsigned kPolEvalAttn = pol_bit(PolicyKind::EvalF32Attn) | pol_bit(PolicyKind::EvalF32AttnLn);
+// the frame-stacked float32 MlpPolicy, rollout and evaluation: the systems the other stacked
+// kinds run (LORENZ3 / PMSM / HR)
+constexpr unsigned kPolMlpStack = pol_bit(PolicyKind::F32MlpStack) | pol_bit(PolicyKind::EvalF32MlpStack);
 
 // Host-side facts of a system, read off its Sys type (lz_systems.h) through the system
 // list (lz_dispatch.h sys_info_of)
@@ -655,6 +685,9 @@ int launch_policy(PolicyKind kind, int system, int n_stack, const KArgs& a, cons
 // per 32-env tile: there is no critic to split off) / 16-env waves, 8 per workgroup
 PolShape eval_f32_policy_shape(int64_t n, int num_cus, int variant);
 PolShape eval_attn_f32_policy_shape(int64_t n, int num_cus, int variant);
+// the frame-stacked float32 MlpPolicy (kStk* blob, 50 KB), rollout and evaluation alike:
+// 32 envs per wave, 4 waves, two workgroups per CU (up to 2 num_cus workgroups)
+PolShape stack_f32_policy_shape(int64_t n, int num_cus, int variant);
 int launch_policy_moments_final(const double* partials, int nparts, int width, double count,
                                 double* out, void* stream);
 

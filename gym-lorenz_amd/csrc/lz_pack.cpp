@@ -179,6 +179,38 @@ void pack_net_f32(uint8_t* net, int O, int rows3, const float* w1, const float* 
   for (int j = 0; j < rows3; ++j) hb[j] = b3[j];
 }
 
+// frame-stacked float32 MlpPolicy net, 64 units (kStk* layout, see mlp_stack_f32 /
+// lz_internal.h): pack_net_f32's maps with 2 out tiles and 12 layer-1 k-steps
+void pack_net_stack_f32(uint8_t* net, int O, int rows3, const float* w1, const float* b1, const float* w2,
+                        const float* b2, const float* w3, const float* b3) {
+  constexpr int H = lz::kStkHidden, KS = lz::kStkKS1;
+  float* f1 = reinterpret_cast<float*>(net + lz::kStkW1);
+  float* f2 = reinterpret_cast<float*>(net + lz::kStkW2);
+  float* c1 = reinterpret_cast<float*>(net + lz::kStkB1);
+  float* c2 = reinterpret_cast<float*>(net + lz::kStkB2);
+  float* hw = reinterpret_cast<float*>(net + lz::kStkH);
+  float* hb = reinterpret_cast<float*>(net + lz::kStkHB);
+  for (int lane = 0; lane < 64; ++lane) {
+    const int r = lane & 31, h = lane >> 5;
+    for (int t = 0; t < 2; ++t) {
+      for (int s = 0; s < KS; ++s) {  // layer 1: k-step s = input 2s + h
+        const int k = 2 * s + h;
+        f1[(t * 64 + lane) * KS + s] = k < O ? w1[(32 * t + r) * O + k] : 0.0f;
+      }
+      for (int q = 0; q < 32; ++q)  // layer 2: k-step q = input unit 32 (q >> 4) + row(q & 15, h)
+        f2[((t * 8 + q / 4) * 64 + lane) * 4 + q % 4] = w2[(32 * t + r) * H + 32 * (q >> 4) + row_of(q & 15, h)];
+    }
+  }
+  for (int h = 0; h < 2; ++h)
+    for (int g = 0; g < 16; ++g)
+      for (int t = 0; t < 2; ++t) {
+        c1[(2 * t + h) * 16 + g] = b1[32 * t + row_of(g, h)];
+        c2[(2 * t + h) * 16 + g] = b2[32 * t + row_of(g, h)];
+        for (int j = 0; j < rows3; ++j) hw[(j * 2 + h) * 32 + t * 16 + g] = w3[j * H + 32 * t + row_of(g, h)];
+      }
+  for (int j = 0; j < rows3; ++j) hb[j] = b3[j];
+}
+
 // Attention-extractor actor-critic (kAtt* layout, see lz_internal.h / attn_extract).
 // log2(e) / sqrt(head_dim 4): the Q projection is stored pre-scaled so that the
 // kernel's softmax is exp2(s - max) on q.k directly.
@@ -518,6 +550,8 @@ lz_status check_dims(int obs_dim, int act_dim, int max_in) {
   if (obs_dim < 1 || obs_dim > max_in || act_dim < 1 || act_dim > lz::kPolMaxAct)
     return pfail(LZ_ERR_UNSUPPORTED, max_in == lz::kPolMaxObs
                                          ? "policy supports obs_dim 1..8 and act_dim 1..4"
+                                     : max_in == lz::kStkMaxIn
+                                         ? "policy supports input dims 1..24 and act_dim 1..4"
                                          : "policy supports input dims 1..32 and act_dim 1..4");
   return LZ_OK;
 }
@@ -677,6 +711,28 @@ lz_status lz_policy_pack_i8x4(const lz_mlp_policy* p, int32_t hidden, void* host
   return pack_mlp_f32(p, hidden, host_blob, cap, true);
 }
 
+int64_t lz_policy_stack_f32_blob_bytes(void) { return lz::kStkBlobBytes; }
+
+// the refusals in lz_policy_pack_hidden's order: policy, hidden, dims, pointers, blob
+lz_status lz_policy_pack_stack_f32(const lz_mlp_policy* p, int32_t hidden, void* host_blob, int64_t cap) {
+  if (!p) return pfail(LZ_ERR_INVALID, "policy is NULL");
+  if (lz_status s = check_hidden(hidden)) return s;
+  if (hidden != lz::kStkHidden)
+    return pfail(LZ_ERR_UNSUPPORTED, "the frame-stacked MlpPolicy runs 64-unit nets only");
+  if (lz_status s = check_dims(p->obs_dim, p->act_dim, lz::kStkMaxIn)) return s;
+  if (lz_status s = check_mlp_ptrs(p)) return s;
+  if (lz_status s = check_blob(p, host_blob, cap, lz::kStkBlobBytes)) return s;
+  const int O = p->obs_dim, A = p->act_dim;
+  uint8_t* b = static_cast<uint8_t*>(host_blob);
+  std::memset(b, 0, lz::kStkBlobBytes);
+  pack_net_stack_f32(b, O, A, p->pi_w1, p->pi_b1, p->pi_w2, p->pi_b2, p->act_w, p->act_b);
+  pack_net_stack_f32(b + lz::kStkNet, O, 1, p->vf_w1, p->vf_b1, p->vf_w2, p->vf_b2, p->val_w, p->val_b);
+  pack_gauss(reinterpret_cast<float*>(b + lz::kStkLogStd), A, p->log_std);
+  lz::blob_tag(LZ_BLOB_MLP_STACK_F32, reinterpret_cast<uint32_t*>(b + lz::kStkTag));
+  write_tanh_table(reinterpret_cast<float*>(b + lz::kStkTanh));
+  return LZ_OK;
+}
+
 int64_t lz_attn_policy_blob_bytes(void) { return lz::kAttBlobBytes; }
 
 lz_status lz_attn_policy_pack(const lz_attn_policy* p, void* host_blob, int64_t cap) {
@@ -754,6 +810,10 @@ int32_t lz_policy_blob_format(const void* host_blob, int64_t size) {
     std::memcpy(t, b + lz::kF32Tag, 16);
     for (uint32_t f : {LZ_BLOB_MLP_F32, LZ_BLOB_MLP_I8X4})
       if (lz::blob_tag_ok(t, f)) return (int32_t)f;
+  }
+  if (size >= lz::kStkBlobBytes) {
+    std::memcpy(t, b + lz::kStkTag, 16);
+    if (lz::blob_tag_ok(t, LZ_BLOB_MLP_STACK_F32)) return LZ_BLOB_MLP_STACK_F32;
   }
   return LZ_BLOB_UNKNOWN;
 }

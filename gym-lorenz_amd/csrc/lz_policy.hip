@@ -2672,6 +2672,285 @@ __global__ __launch_bounds__(256) void k_trace_slots(int32_t* slot_map, int64_t 
 #include "lz_eval_kernels.inc"
 #undef LZ_EVAL_TRACE
 
+// ---------------------------------------------------------------------------------------
+// The float32 MlpPolicy on a 4-frame VecFrameStack (code/lorenz_filter/train.py:109-131:
+// PPO("MlpPolicy") on VecFrameStack(n_stack=4); test_evaluate.py:94-157 evaluates it): SB3's
+// default 64 x 64 Tanh nets on the 24-wide stacked observation, kStk* blob (lz_internal.h).
+//
+// One net on the wave's 32-env tile: the two-tile sibling of mlp_f32 / mlp_f32_tail (those
+// stay as they are: the kernels built from them keep their code).  xs[s] = this lane's
+// layer-1 input for k-step s (stack element 2s + h of env lane & 31).  Every chain is the
+// 128-unit one without its zero-padded steps: layer 1 b1 then inputs 0, 1, ... in order,
+// layer 2 b2 then units 0..63 in the kF32W2 k order, the heads (p0 + p1) + b over the two
+// lane halves.  Returns the NH head rows in head[] on every lane.
+template <int KS1, int NH>
+__device__ __forceinline__ void mlp_stack_f32(const uint8_t* net, const float* xs, int lane, float* head,
+                                              const float* ttab) {
+  static_assert(KS1 <= kStkKS1, "layer-1 k-steps");
+  asm volatile("" ::: "memory");
+  const int h = lane >> 5;
+  const f32x4* w1 = reinterpret_cast<const f32x4*>(net + kStkW1) + lane * (kStkKS1 / 4);
+  const f32x16* b1 = reinterpret_cast<const f32x16*>(net + kStkB1) + h;
+  f32x16 a1[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    f32x4 w[kStkKS1 / 4];
+#pragma unroll
+    for (int e = 0; e < kStkKS1 / 4; ++e) w[e] = w1[t * 64 * (kStkKS1 / 4) + e];
+    f32x16 c = b1[2 * t];
+#pragma unroll
+    for (int s = 0; s < KS1; ++s) c = mfma_f32(w[s >> 2][s & 3], xs[s], c);
+#pragma unroll
+    for (int g = 0; g < 16; ++g) c[g] = tanh_tab(c[g], ttab);
+    a1[t] = c;
+  }
+  const f32x4* w2 = reinterpret_cast<const f32x4*>(net + kStkW2) + lane;
+  const f32x16* b2 = reinterpret_cast<const f32x16*>(net + kStkB2) + h;
+  const float* wh = reinterpret_cast<const float*>(net + kStkH) + h * 32;
+  const float* bh = reinterpret_cast<const float*>(net + kStkHB);
+  float acc[NH];
+#pragma unroll
+  for (int j = 0; j < NH; ++j) acc[j] = 0.0f;  // first step fmaf(w, v, +0)
+#pragma unroll 1
+  for (int t = 0; t < 2; ++t) {
+    f32x16 c = b2[2 * t];
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti) {
+      asm volatile("" ::: "memory");
+      f32x4 wq[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) wq[e] = w2[((t * 8) + ti * 4 + e) * 64];
+#pragma unroll
+      for (int g = 0; g < 16; ++g) c = mfma_f32(wq[g >> 2][g & 3], a1[ti][g], c);
+    }
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+      const float v = tanh_tab(c[g], ttab);
+#pragma unroll
+      for (int j = 0; j < NH; ++j) acc[j] = fmaf(wh[j * 64 + t * 16 + g], v, acc[j]);
+      if ((g & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NH; ++j) {
+    const float o = __shfl_xor(acc[j], 32, 64);
+    head[j] = (acc[j] + o) + bh[j];  // IEEE add commutes: both halves get the same bits
+  }
+}
+
+// this lane half's layer-1 inputs from the env's stack (both halves hold all of it)
+template <int SO, int KS1>
+__device__ __forceinline__ void stack_inputs_f32(const float* st, int h, float* xs) {
+#pragma unroll
+  for (int s = 0; s < KS1; ++s) {
+    const float hi = 2 * s + 1 < SO ? st[2 * s + 1 < SO ? 2 * s + 1 : 0] : 0.0f;
+    xs[s] = h ? hi : st[2 * s];
+  }
+}
+
+// The rollout: k_rollout_policy's kMlpF32 loop (each wave a 32-env tile, the two nets one
+// after the other) with its kAttnLn frame stack, step for step -- the stack in the
+// registers of both lane halves of the env; obs_buf gets the stacked observation the policy
+// saw; SB3 StackedObservations.update after the env step.  No VecNormalize (refused by the
+// entry point).
+template <class Sys, int W, int S = 4>
+__global__ __launch_bounds__(W * 64, 2) void k_rollout_policy_stack_f32(KArgs a, PArgs p) {
+  constexpr int E = 32;
+  constexpr int O = Sys::O, A = Sys::A, SO = S * O, KS1 = (SO + 1) / 2;
+  static_assert(SO <= kStkMaxIn && O <= kPolMaxObs && A <= kPolMaxAct, "policy tile shape");
+  static_assert(kStkBlobBytes % 16 == 0 && kStkNet % 16 == 0, "16-B pieces");
+  __shared__ __attribute__((aligned(64))) uint8_t s_blob[kStkBlobBytes];
+  __shared__ double s_norm[2 * kPolMaxObs];
+  const int tid = (int)threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6, h = lane >> 5;
+  const int slot = lane & 31;
+  blob_to_lds(reinterpret_cast<f4v*>(s_blob), reinterpret_cast<const f4v*>(p.blob), kStkBlobBytes / 16, tid,
+              W * 64, !blob_is(p.blob, kStkTag, LZ_BLOB_MLP_STACK_F32));
+  const uint64_t tick = pol_prologue<O>(a, p, s_norm, tid);
+  __syncthreads();
+  const uint8_t* pi_net = s_blob;
+  const uint8_t* vf_net = s_blob + kStkNet;
+  const float* g_scale = reinterpret_cast<const float*>(s_blob + kStkLogStd) + 4;
+  const float* ttab = reinterpret_cast<const float*>(s_blob + kStkTanh);
+  const bool det = (p.pflags & LZ_POLICY_DETERMINISTIC) != 0;
+  const bool boot = (p.pflags & LZ_POLICY_BOOTSTRAP) != 0;
+  const float gamma = p.gamma;
+  Sys sys;
+  sys.setup(a);
+  float* obs_buf = static_cast<float*>(a.obs);
+  float* rew_buf = static_cast<float*>(a.rew);
+  const int64_t ntiles = (a.n + E - 1) / E;
+  for (int64_t tile = (int64_t)blockIdx.x * W + wave; tile < ntiles; tile += (int64_t)gridDim.x * W) {
+    const int64_t i = tile * E + slot;
+    const bool valid = i < a.n;       // both lanes of the env
+    const bool live = valid && h == 0;  // the lane that steps and stores it
+    int32_t steps;
+    bool any_reset = false;
+    float o[O];
+    tile_open(sys, a, p, i, live, steps, o);
+    float st[SO];
+#pragma unroll
+    for (int j = 0; j < SO; ++j) st[j] = valid ? p.stack_in[i * SO + j] : 0.0f;
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): settle the tile's loads outside the step loop
+    for (int k = 0; k < a.K; ++k) {
+      const int64_t off = (int64_t)k * a.n + i;
+      if (live) {  // the stacked observation the policy sees
+#pragma unroll
+        for (int j = 0; j < SO; ++j) obs_buf[off * SO + j] = st[j];
+      }
+      float mean[A], val[1];
+      {
+        float xs[KS1];
+        stack_inputs_f32<SO, KS1>(st, h, xs);
+        mlp_stack_f32<KS1, A>(pi_net, xs, lane, mean, ttab);
+        __builtin_amdgcn_sched_barrier(0);  // the two nets one after the other
+        mlp_stack_f32<KS1, 1>(vf_net, xs, lane, val, ttab);
+      }
+      float act_c[A];
+      if (live) {
+        float act[A];
+        const float lp = policy_sample<A, true>(a, p, i, tick + (uint64_t)k, det, mean, g_scale, act, act_c);
+#pragma unroll
+        for (int j = 0; j < A; ++j) p.act[off * A + j] = act[j];
+        p.logp[off] = lp;
+        p.val[off] = val[0];
+      }
+      float on[O], ot[O];
+      float rew = 0.0f;
+      bool did_reset;
+      const uint8_t df = step_body<Sys, float, true, true>(sys, steps, a, i, live, act_c,
+                                                           tick + (uint64_t)k, k, on, rew, did_reset, ot);
+      any_reset = any_reset || did_reset;
+      // VecFrameStack (SB3 StackedObservations.update), as k_rollout_policy's kAttnLn block:
+      // the partner half receives the env's new / terminal frames and done byte; both halves
+      // roll the stack; a done env's terminal observation is [rolled stack, terminal frame],
+      // its stack restarts from zeros; the new frame goes last
+      const uint8_t db = (uint8_t)__shfl((int)df, slot, 64);
+      float nb[O], tb[O];
+#pragma unroll
+      for (int j = 0; j < O; ++j) {
+        nb[j] = __shfl(on[j], slot, 64);
+        tb[j] = __shfl(ot[j], slot, 64);
+      }
+      if (boot) {  // SB3: truncated (not terminated) -> rewards += gamma * V(stacked terminal obs)
+        const bool bt = valid && is_truncation(db);
+        if (__ballot(bt) != 0ull) {  // wave-uniform branch
+          float stt[SO], xs[KS1], vt[1];
+#pragma unroll
+          for (int j = 0; j < SO - O; ++j) stt[j] = st[j + O];
+#pragma unroll
+          for (int j = 0; j < O; ++j) stt[SO - O + j] = tb[j];
+          stack_inputs_f32<SO, KS1>(stt, h, xs);
+          mlp_stack_f32<KS1, 1>(vf_net, xs, lane, vt, ttab);
+          if (bt) rew = rew + gamma * vt[0];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < SO - O; ++j) st[j] = db ? 0.0f : st[j + O];
+#pragma unroll
+      for (int j = 0; j < O; ++j) st[SO - O + j] = nb[j];
+      if (live) {
+        rew_buf[off] = rew;
+        a.done[off] = df;
+      }
+#pragma unroll
+      for (int j = 0; j < O; ++j) o[j] = on[j];
+    }
+    float vl[1];
+    {
+      float xs[KS1];
+      stack_inputs_f32<SO, KS1>(st, h, xs);
+      mlp_stack_f32<KS1, 1>(vf_net, xs, lane, vl, ttab);
+    }
+    if (live) {
+#pragma unroll
+      for (int j = 0; j < SO; ++j) p.stack_out[i * SO + j] = st[j];
+      p.last_val[i] = vl[0];
+    }
+    tile_close(sys, a, p, i, live, steps, any_reset, o);
+  }
+}
+
+// The evaluation: k_evaluate_policy_f32's loop (the pi net, the Normal constants and the
+// tanh table alone in LDS; the [24, N] float64 table through eval_step / eval_store) on
+// the frame stack above.  There is no traced form.
+template <class Sys, int W, int S = 4>
+__global__ __launch_bounds__(W * 64, 2) void k_evaluate_policy_stack_f32(KArgs a, PArgs p, EArgs ev) {
+  constexpr int E = 32;
+  constexpr int O = Sys::O, A = Sys::A, ED = O / 2, SO = S * O, KS1 = (SO + 1) / 2;
+  constexpr int kCst = 64 + kTanhSegs * 32;
+  static_assert(SO <= kStkMaxIn && O <= kPolMaxObs && A <= kPolMaxAct && ED <= 4, "policy tile shape");
+  static_assert(kStkNet % 16 == 0 && kStkLogStd % 16 == 0 && kCst % 16 == 0 && kStkTag + 16 <= kStkNet,
+                "16-B pieces");
+  __shared__ __attribute__((aligned(64))) uint8_t s_net[kStkNet];
+  __shared__ __attribute__((aligned(16))) uint8_t s_cst[kCst];
+  __shared__ double s_norm[2 * kPolMaxObs];
+  const int tid = (int)threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6, h = lane >> 5;
+  const int slot = lane & 31;
+  const bool bad = !blob_is(p.blob, kStkTag, LZ_BLOB_MLP_STACK_F32);
+  blob_to_lds(reinterpret_cast<f4v*>(s_net), reinterpret_cast<const f4v*>(p.blob), kStkNet / 16, tid, W * 64,
+              bad);
+  blob_to_lds(reinterpret_cast<f4v*>(s_cst), reinterpret_cast<const f4v*>(p.blob + kStkLogStd), kCst / 16,
+              tid, W * 64, bad);
+  const uint64_t tick = pol_prologue<O>(a, p, s_norm, tid);
+  __syncthreads();
+  const float* g_scale = reinterpret_cast<const float*>(s_cst) + 4;
+  const float* ttab = reinterpret_cast<const float*>(s_cst + 64);
+  const bool det = (p.pflags & LZ_POLICY_DETERMINISTIC) != 0;
+  const bool autoreset = (a.flags & LZ_FLAG_AUTORESET) != 0;
+  Sys sys;
+  sys.setup(a);
+  const int64_t ntiles = (a.n + E - 1) / E;
+  for (int64_t tile = (int64_t)blockIdx.x * W + wave; tile < ntiles; tile += (int64_t)gridDim.x * W) {
+    const int64_t i = tile * E + slot;
+    const bool valid = i < a.n;
+    const bool live = valid && h == 0;
+    int32_t steps;
+    bool any_reset = false;
+    double q[4][4];  // this tile's accumulators: zeroed per grid-stride tile
+    EvalCount c;
+    eval_zero<4>(q, c);
+    float o[O];
+    tile_open(sys, a, p, i, live, steps, o);
+    float st[SO];
+#pragma unroll
+    for (int j = 0; j < SO; ++j) st[j] = valid ? p.stack_in[i * SO + j] : 0.0f;
+    for (int k = 0; k < a.K; ++k) {
+      float mean[A], xs[KS1];
+      stack_inputs_f32<SO, KS1>(st, h, xs);
+      mlp_stack_f32<KS1, A>(s_net, xs, lane, mean, ttab);
+      float act_c[A];
+      if (live) {
+        float act[A];
+        policy_sample<A, false>(a, p, i, tick + (uint64_t)k, det, mean, g_scale, act, act_c);
+      }
+      float on[O], ot[O];
+      float rew = 0.0f;
+      bool did_reset;
+      const uint8_t df = step_body<Sys, float, true, true>(sys, steps, a, i, live, act_c,
+                                                           tick + (uint64_t)k, k, on, rew, did_reset, ot);
+      any_reset = any_reset || did_reset;
+      if (live) eval_step<4, ED>(q, c, 0, ot, rew, df, k, autoreset, ev.skip, ev.max_episodes);
+      // VecFrameStack: roll, a done env's older frames restart from zeros, the new frame last
+      const uint8_t db = (uint8_t)__shfl((int)df, slot, 64);
+#pragma unroll
+      for (int j = 0; j < SO - O; ++j) st[j] = db ? 0.0f : st[j + O];
+#pragma unroll
+      for (int j = 0; j < O; ++j) {
+        st[SO - O + j] = __shfl(on[j], slot, 64);
+        o[j] = on[j];
+      }
+    }
+    tile_close(sys, a, p, i, live, steps, any_reset, o);
+    if (live) {
+      eval_store<4>(ev.stats, a.n, i, q, c, 0, true, bad);
+#pragma unroll
+      for (int j = 0; j < SO; ++j) p.stack_out[i * SO + j] = st[j];
+    }
+  }
+}
+
 // obs moments: out = (count, column sums, column sums of squares) from the per-wave
 // partials, summed in a fixed order.  One workgroup per column (the column loop ran in
 // a single workgroup before: 22.9 us per collect at 262,144 envs, 2.8% of K=16); the
@@ -2983,6 +3262,36 @@ static int launch_eval_attn_f32(int ln, int n_stack, const KArgs& a, const PArgs
   return (int)hipGetLastError();
 }
 
+// The frame-stacked float32 MlpPolicy, rollout and evaluation: 4 waves of 32 envs (one per
+// SIMD) per workgroup and two workgroups per CU (two waves per SIMD, 256 registers each:
+// the 50 KB blob would admit a third, the PMSM / HR kernels' registers do not), so up to
+// 2 num_cus workgroups
+PolShape stack_f32_policy_shape(int64_t n, int num_cus, int) {
+  PolShape s = {32, 4, 0, 0};
+  const int64_t groups = ((n + 31) / 32 + s.waves - 1) / s.waves;
+  const int64_t cap = 2 * (int64_t)num_cus;
+  s.grid = (int)(groups < cap ? groups : cap);
+  return s;
+}
+
+template <class Sys>
+static int launch_pol_stack_f32(int n_stack, const KArgs& a, const PArgs& p, const PolShape& sh,
+                                hipStream_t s) {
+  if (sh.waves != 4 || n_stack != 4) return (int)hipErrorInvalidValue;  // stack_f32_policy_shape's
+  hipLaunchKernelGGL((k_rollout_policy_stack_f32<Sys, 4, 4>), dim3((unsigned)sh.grid), dim3(4 * 64), 0, s, a,
+                     p);
+  return (int)hipGetLastError();
+}
+
+template <class Sys>
+static int launch_eval_stack_f32(int n_stack, const KArgs& a, const PArgs& p, const EArgs& ev,
+                                 const PolShape& sh, hipStream_t s) {
+  if (sh.waves != 4 || n_stack != 4) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL((k_evaluate_policy_stack_f32<Sys, 4, 4>), dim3((unsigned)sh.grid), dim3(4 * 64), 0, s,
+                     a, p, ev);
+  return (int)hipGetLastError();
+}
+
 // One entry for every policy rollout: the system picks the Sys type, the kind the
 // launcher; a kind the system list (lz_dispatch.h) does not name for the system is not
 // instantiated for it and refused here (lz_api.cpp refuses it first, with a message).
@@ -3030,6 +3339,14 @@ int launch_policy(PolicyKind kind, int system, int n_stack, const KArgs& a, cons
       case PolicyKind::EvalF32AttnLn:
         if constexpr (Tag::runs(PolicyKind::EvalF32AttnLn)) {
           if (ev) return launch_eval_attn_f32<Sys>(1, n_stack, a, p, *ev, tr, sh, s);
+        }
+        break;
+      case PolicyKind::F32MlpStack:
+        if constexpr (Tag::runs(PolicyKind::F32MlpStack)) return launch_pol_stack_f32<Sys>(n_stack, a, p, sh, s);
+        break;
+      case PolicyKind::EvalF32MlpStack:
+        if constexpr (Tag::runs(PolicyKind::EvalF32MlpStack)) {
+          if (ev && !tr) return launch_eval_stack_f32<Sys>(n_stack, a, p, *ev, sh, s);
         }
         break;
     }

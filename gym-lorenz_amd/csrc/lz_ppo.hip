@@ -90,7 +90,21 @@ struct GradArgs {
 #include "lz_grad_body.inc"
 #undef LZ_GRAD_KERNEL
 #undef LZ_GRAD_H
+// ... and for that net on a frame-stacked observation of up to 24 inputs
+// (code/lorenz_filter/train.py:109-131: VecFrameStack(n_stack=4) on HR's 6, tensors
+// (64, 24) / (64, 64) / (A, 64)): the x and W1 images 24 wide, 12 layer-1 MFMA steps
+// (lz_ppo_grad_wide_f32 for obs_dim > 8)
+#define LZ_GRAD_H 64
+#define LZ_GRAD_MAXO 24
+#define LZ_GRAD_KERNEL k_ppo_grad_h64_wide
+#include "lz_grad_body.inc"
+#undef LZ_GRAD_KERNEL
+#undef LZ_GRAD_MAXO
+#undef LZ_GRAD_H
 #undef LZ_GRAD_PPO
+
+constexpr int kWideMaxO = 24;  // LZ_GRAD_MAXO of k_ppo_grad_h64_wide
+inline bool wide_dims_ok(int O, int A) { return O >= 1 && O <= kWideMaxO && A >= 1 && A <= kMaxA; }
 
 // out[i] = the slots' entries i added in slot order (nothing after the stop, as k_ppo_grad)
 __global__ __launch_bounds__(256) void k_ppo_reduce(const double* __restrict__ part, int nwg,
@@ -259,6 +273,22 @@ extern "C" int64_t lz_ppo_workspace_bytes_hidden(int64_t n_samples, int32_t obs_
   return (int64_t)wgs_per_net(n_samples, max_workgroups) * (P + kTail) * (int64_t)sizeof(double);
 }
 
+extern "C" int64_t lz_ppo_param_count_wide(int32_t obs_dim, int32_t act_dim, int32_t hidden) {
+  using namespace lz::ppo;
+  if (!wide_dims_ok(obs_dim, act_dim) || hidden != kH64) return -1;
+  return layout(obs_dim, act_dim, hidden).P;
+}
+
+extern "C" int64_t lz_ppo_workspace_bytes_wide(int64_t n_samples, int32_t obs_dim, int32_t act_dim,
+                                               int32_t hidden, int32_t max_workgroups) {
+  using namespace lz::ppo;
+  if (!wide_dims_ok(obs_dim, act_dim) || hidden != kH64 || n_samples < 1 || max_workgroups < 0 ||
+      max_workgroups > kMaxWgs)
+    return -1;
+  const int64_t P = layout(obs_dim, act_dim, hidden).P;
+  return (int64_t)wgs_per_net(n_samples, max_workgroups) * (P + kTail) * (int64_t)sizeof(double);
+}
+
 extern "C" lz_status lz_ppo_adv_moments(const float* advantages, const int32_t* indices,
                                         int64_t n_samples, int64_t n_rows, void* workspace,
                                         double* out, int32_t device, void* stream) {
@@ -285,10 +315,11 @@ lz_status fail(lz_status s, const char* who, const char* what) {
   return lz::set_error(s, m);
 }
 
-// lz_ppo_grad_f32 (any_hidden false: 128 units only) and lz_ppo_grad_hidden_f32: the same
-// refusals in the same order, then the launch of the form built for g->hidden
+// lz_ppo_grad_f32 (any_hidden false: 128 units only), lz_ppo_grad_hidden_f32 and
+// lz_ppo_grad_wide_f32 (wide: obs_dim up to 24, 64 units only): the same refusals in the
+// same order, then the launch of the form built for g->hidden (and, wide, g->obs_dim)
 lz_status grad_entry(const lz_ppo_grad_args* g, int32_t device, void* stream, const char* who,
-                     bool any_hidden) {
+                     bool any_hidden, bool wide = false) {
   using namespace lz::ppo;
   if (!g) return fail(LZ_ERR_INVALID, who, "NULL args");
   if (!g->params || !g->observations || !g->actions || !g->advantages || !g->returns ||
@@ -296,8 +327,9 @@ lz_status grad_entry(const lz_ppo_grad_args* g, int32_t device, void* stream, co
     return fail(LZ_ERR_INVALID, who, "NULL buffer");
   if (g->clip_range_vf > 0.0 && !g->old_values)
     return fail(LZ_ERR_INVALID, who, "NULL old_values with clip_range_vf > 0");
-  if (!dims_ok(g->obs_dim, g->act_dim))
-    return fail(LZ_ERR_INVALID, who, "obs_dim must be 1..8 and act_dim 1..4");
+  if (wide ? !wide_dims_ok(g->obs_dim, g->act_dim) : !dims_ok(g->obs_dim, g->act_dim))
+    return fail(LZ_ERR_INVALID, who, wide ? "obs_dim must be 1..24 and act_dim 1..4"
+                                          : "obs_dim must be 1..8 and act_dim 1..4");
   if (g->n_samples < 1) return fail(LZ_ERR_INVALID, who, "n_samples < 1");
   if (g->n_rows < 1) return fail(LZ_ERR_INVALID, who, "n_rows < 1");
   if (!g->indices && g->n_samples > g->n_rows)
@@ -308,13 +340,18 @@ lz_status grad_entry(const lz_ppo_grad_args* g, int32_t device, void* stream, co
     return fail(LZ_ERR_INVALID, who, "clip_range_vf must be finite");
   if (g->max_workgroups < 0 || g->max_workgroups > kMaxWgs)
     return fail(LZ_ERR_INVALID, who, "max_workgroups must be 0..4096");
-  if (any_hidden ? !hidden_ok(g->hidden) : g->hidden != kH)
-    return fail(LZ_ERR_UNSUPPORTED, who, any_hidden ? "hidden must be 64 or 128" : "hidden must be 128");
-  const int64_t need = lz_ppo_workspace_bytes_hidden(g->n_samples, g->obs_dim, g->act_dim, g->hidden,
-                                                     g->max_workgroups);
+  if (wide ? g->hidden != kH64 : any_hidden ? !hidden_ok(g->hidden) : g->hidden != kH)
+    return fail(LZ_ERR_UNSUPPORTED, who, wide         ? "hidden must be 64"
+                                         : any_hidden ? "hidden must be 64 or 128"
+                                                      : "hidden must be 128");
+  const int64_t need =
+      wide ? lz_ppo_workspace_bytes_wide(g->n_samples, g->obs_dim, g->act_dim, g->hidden, g->max_workgroups)
+           : lz_ppo_workspace_bytes_hidden(g->n_samples, g->obs_dim, g->act_dim, g->hidden,
+                                           g->max_workgroups);
   if (g->workspace_bytes < need)
-    return fail(LZ_ERR_INVALID, who, any_hidden ? "workspace smaller than lz_ppo_workspace_bytes_hidden"
-                                                : "workspace smaller than lz_ppo_workspace_bytes");
+    return fail(LZ_ERR_INVALID, who, wide         ? "workspace smaller than lz_ppo_workspace_bytes_wide"
+                                     : any_hidden ? "workspace smaller than lz_ppo_workspace_bytes_hidden"
+                                                  : "workspace smaller than lz_ppo_workspace_bytes");
   if (hipSetDevice(device) != hipSuccess) return lz::set_error(LZ_ERR_HIP, "hipSetDevice failed");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nwg = wgs_per_net(g->n_samples, g->max_workgroups);
@@ -342,7 +379,9 @@ lz_status grad_entry(const lz_ppo_grad_args* g, int32_t device, void* stream, co
   a.clip_hi = (float)(1.0 + g->clip_range);
   a.clip_vf = (float)g->clip_range_vf;
   a.part = static_cast<double*>(g->workspace);
-  if (g->hidden == kH64)
+  if (g->hidden == kH64 && g->obs_dim > kMaxO)  // wide only: the others refused it above
+    hipLaunchKernelGGL(k_ppo_grad_h64_wide, dim3(2u * (unsigned)nwg), dim3(2 * kH64), 0, s, a);
+  else if (g->hidden == kH64)
     hipLaunchKernelGGL(k_ppo_grad_h64, dim3(2u * (unsigned)nwg), dim3(2 * kH64), 0, s, a);
   else
     hipLaunchKernelGGL(k_ppo_grad, dim3(2u * (unsigned)nwg), dim3(2 * kH), 0, s, a);
@@ -361,6 +400,10 @@ extern "C" lz_status lz_ppo_grad_f32(const lz_ppo_grad_args* g, int32_t device, 
 
 extern "C" lz_status lz_ppo_grad_hidden_f32(const lz_ppo_grad_args* g, int32_t device, void* stream) {
   return grad_entry(g, device, stream, "lz_ppo_grad_hidden_f32", true);
+}
+
+extern "C" lz_status lz_ppo_grad_wide_f32(const lz_ppo_grad_args* g, int32_t device, void* stream) {
+  return grad_entry(g, device, stream, "lz_ppo_grad_wide_f32", true, true);
 }
 
 extern "C" lz_status lz_adam_apply_f32(const lz_adam_apply_args* p, int32_t device, void* stream) {

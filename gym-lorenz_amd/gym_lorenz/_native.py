@@ -87,7 +87,7 @@ class LzInfo(ctypes.Structure):
 POLICY_DETERMINISTIC, POLICY_BOOTSTRAP, POLICY_I8X4 = 1, 2, 4
 # lz_policy_blob_format: the format tag every float32 / i8x4 packer writes (LZ_BLOB_*)
 (BLOB_UNKNOWN, BLOB_MLP_F32, BLOB_MLP_I8X4, BLOB_ATTN_F32, BLOB_ATTN_I8X4, BLOB_ATTN_LN_F32,
- BLOB_ATTN_LN_I8X4) = range(7)
+ BLOB_ATTN_LN_I8X4, BLOB_MLP_STACK_F32) = range(8)
 POLICY_HIDDEN = 128
 
 
@@ -294,11 +294,12 @@ class LzLaunchShape(ctypes.Structure):
 (CALL_STEP, CALL_ROLLOUT, CALL_ROLLOUT_POLICY, CALL_ROLLOUT_POLICY_F32, CALL_POLICY_STEP_F32,
  CALL_ROLLOUT_POLICY_ATTN, CALL_ROLLOUT_POLICY_ATTN_STACK, CALL_ROLLOUT_POLICY_ATTN_F32,
  CALL_ROLLOUT_POLICY_ATTN_STACK_F32, CALL_STEP_NOISE, CALL_EVALUATE_POLICY_F32,
- CALL_EVALUATE_POLICY_ATTN_F32, CALL_EVALUATE_POLICY_ATTN_STACK_F32) = range(13)
+ CALL_EVALUATE_POLICY_ATTN_F32, CALL_EVALUATE_POLICY_ATTN_STACK_F32,
+ CALL_ROLLOUT_POLICY_STACK_F32, CALL_EVALUATE_POLICY_STACK_F32) = range(15)
 KERNELS = {1: "step", 2: "step_multi", 3: "rollout", 4: "rollout_wave", 5: "rollout_split",
            6: "policy", 7: "policy_pair", 8: "policy_pair_pipe", 9: "policy_split",
            10: "policy_step", 11: "policy_attn", 12: "policy_attn_f32", 13: "rollout_pair",
-           14: "eval", 15: "eval_attn_f32"}
+           14: "eval", 15: "eval_attn_f32", 16: "policy_stack_f32", 17: "eval_stack_f32"}
 SHAPE_NO_DONE, SHAPE_GRID_STRIDE = 1, 2
 
 VP = ctypes.c_void_p
@@ -349,6 +350,13 @@ _SIGS = {
     "lz_policy_pack_f32": (ctypes.c_int, [ctypes.POINTER(LzMlpPolicy), ctypes.c_int32, VP,
                                           ctypes.c_int64]),
     "lz_rollout_policy_f32": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyRolloutArgs)]),
+    "lz_policy_stack_f32_blob_bytes": (ctypes.c_int64, []),
+    "lz_policy_pack_stack_f32": (ctypes.c_int, [ctypes.POINTER(LzMlpPolicy), ctypes.c_int32, VP,
+                                                ctypes.c_int64]),
+    "lz_stack_rollout_policy_f32": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyRolloutArgs),
+                                                   ctypes.c_int32, VP, VP]),
+    "lz_stack_evaluate_policy_f32": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyEvalArgs),
+                                                    ctypes.c_int32, VP, VP]),
     "lz_policy_step_f32": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyRolloutArgs), ctypes.c_int32, VP,
                                           VP]),
     "lz_rollout_policy_f32_vn": (ctypes.c_int, [VP, ctypes.POINTER(LzPolicyRolloutArgs), VP]),
@@ -403,6 +411,10 @@ _SIGS = {
     "lz_ppo_workspace_bytes_hidden": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                                        ctypes.c_int32, ctypes.c_int32]),
     "lz_ppo_grad_hidden_f32": (ctypes.c_int, [ctypes.POINTER(LzPpoGradArgs), ctypes.c_int32, VP]),
+    "lz_ppo_param_count_wide": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "lz_ppo_workspace_bytes_wide": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                     ctypes.c_int32, ctypes.c_int32]),
+    "lz_ppo_grad_wide_f32": (ctypes.c_int, [ctypes.POINTER(LzPpoGradArgs), ctypes.c_int32, VP]),
     "lz_episode_starts": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, VP, VP, VP, VP,
                                          ctypes.c_int32, VP]),
     "lz_frame_stack": (ctypes.c_int, [VP, VP, VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,

@@ -399,12 +399,27 @@ _PACKERS = {
                           nat.BLOB_ATTN_LN_I8X4),
 }
 
+# The frame-stacked MlpPolicy (code/lorenz_filter/train.py:109-131: PPO("MlpPolicy") on
+# VecFrameStack(n_stack=4), SB3's default 64 x 64 nets), family "mlp_stack": its rows of the
+# two tables, kept beside them -- float32 only, no traced evaluation.
+STACK_HIDDEN = 64
+_STACK_PACKERS = {
+    ("mlp_stack", "fp32"): ("lz_policy_pack_stack_f32", "lz_policy_stack_f32_blob_bytes",
+                            nat.BLOB_MLP_STACK_F32),
+}
+
+
+def _packer_row(family, precision):
+    key = (family, precision)
+    return _STACK_PACKERS[key] if key in _STACK_PACKERS else _PACKERS[key]
+
 
 def _pack(family, precision, state_dict, in_dim, act_dim, features_dim=64):
     """SB3 state_dict -> the uint8 numpy blob of _PACKERS[family, precision] (host; needs
-    no GPU).  in_dim: the policy's input width (the stacked one for "attn_ln")."""
-    pack, blob_bytes, _tag = _PACKERS[family, precision]
-    if family == "mlp":
+    no GPU).  in_dim: the policy's input width (the stacked one for "attn_ln" and
+    "mlp_stack")."""
+    pack, blob_bytes, _tag = _packer_row(family, precision)
+    if family in ("mlp", "mlp_stack"):
         p, H, _keep = _mlp_policy_struct(state_dict, in_dim, act_dim)
         args = (ctypes.byref(p), H)
     else:
@@ -425,6 +440,13 @@ def pack_policy_f32(state_dict, obs_dim, act_dim):
     """lz_policy_pack_f32: SB3 state_dict (net_arch pi=[H,H] vf=[H,H], H <= 128) ->
     uint8 numpy blob of the float32 kernel (host; needs no GPU)."""
     return _pack("mlp", "fp32", state_dict, obs_dim, act_dim)
+
+
+def pack_policy_stack_f32(state_dict, in_dim, act_dim):
+    """lz_policy_pack_stack_f32: code/lorenz_filter/train.py:109-131's policy -- the 64-unit
+    MlpPolicy on VecFrameStack observations (in_dim = the stacked observation width, up to
+    24) -> uint8 numpy blob of the native 64-unit float32 kernel (host; needs no GPU)."""
+    return _pack("mlp_stack", "fp32", state_dict, in_dim, act_dim)
 
 
 def pack_policy_i8x4(state_dict, obs_dim, act_dim):
@@ -495,10 +517,10 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
-def blob_format(attention, attention_ln, i8x4):
+def blob_format(attention, attention_ln, i8x4, mlp_stack=False):
     """The LZ_BLOB_* format a float32 / i8x4 launch reads (entry point + LZ_POLICY_I8X4)."""
-    family = "attn_ln" if attention_ln else "attn" if attention else "mlp"
-    return _PACKERS[family, "i8x4" if i8x4 else "fp32"][2]
+    family = "attn_ln" if attention_ln else "attn" if attention else "mlp_stack" if mlp_stack else "mlp"
+    return _packer_row(family, "i8x4" if i8x4 else "fp32")[2]
 
 
 # The entry points, one row per (kind, family, precision), laid out like kPolicyTable in
@@ -521,6 +543,11 @@ _LAUNCH = {
     ("trace", "attn", "fp32"): "lz_evaluate_policy_attn_f32_trace",
     ("trace", "attn_ln", "fp32"): "lz_evaluate_policy_attn_stack_f32_trace",
 }
+# ... and family "mlp_stack"'s (see _STACK_PACKERS): (n_stack, stack_in, stack_out) as "attn_ln"
+_STACK_LAUNCH = {
+    ("rollout", "mlp_stack", "fp32"): "lz_stack_rollout_policy_f32",
+    ("evaluate", "mlp_stack", "fp32"): "lz_stack_evaluate_policy_f32",
+}
 
 
 class _PolicySeam:
@@ -530,13 +557,14 @@ class _PolicySeam:
     env handle's stream.  A subclass sets env, device, n, O, A, obs_rms and _what."""
 
     _what = "rollout"          # the noun of the refusals
-    attention = attention_ln = False
+    attention = attention_ln = mlp_stack = False
     f32, i8x4 = True, False    # the evaluator's stance; the collector sets its own
     blob = last_obs = last_stack = None
 
     @property
     def family(self):
-        return "attn_ln" if self.attention_ln else "attn" if self.attention else "mlp"
+        return ("attn_ln" if self.attention_ln else "attn" if self.attention
+                else "mlp_stack" if self.mlp_stack else "mlp")
 
     def _init_frame_stack(self, frame_stack):
         # SB3 VecFrameStack(n_stack) between the env and the policy
@@ -551,21 +579,26 @@ class _PolicySeam:
         """The family of the state_dict's keys (as FusedRolloutCollector.set_params says)."""
         self.attention = is_attention_policy(state_dict)
         self.attention_ln = is_attention_ln_policy(state_dict)
-        if self.frame_stack > 1 and not self.attention_ln:
+        # ... or, frame-stacked, the 64-unit MlpPolicy that script trains in fact
+        # (code/lorenz_filter/train.py:109-131: its policy_kwargs are never passed on)
+        w1 = state_dict.get(KEYS[0]) if not self.attention else None
+        self.mlp_stack = (self.frame_stack > 1 and w1 is not None
+                          and tuple(w1.shape) == (STACK_HIDDEN, self.frame_stack * self.O))
+        if self.frame_stack > 1 and not (self.attention_ln or self.mlp_stack):
             raise ValueError("frame_stack > 1 runs code/lorenz_filter/train.py's policy "
                              "(the residual + LayerNorm attention extractor)")
 
     def _pack_params(self, state_dict, precision):
         if self.attention_ln and self.obs_rms is not None:
             raise ValueError("the LayerNorm attention %s takes raw observations" % self._what)
-        in_dim = self.frame_stack * self.O if self.attention_ln else self.O
+        in_dim = self.frame_stack * self.O if (self.attention_ln or self.mlp_stack) else self.O
         return _pack(self.family, precision, state_dict, in_dim, self.A)
 
     def _set_blob(self, blob):
         """Upload a packed blob; a float32 / i8x4 one only if its format tag is the one the
         launch this object makes will expect."""
         if self.f32:
-            want = blob_format(self.attention, self.attention_ln, self.i8x4)
+            want = blob_format(self.attention, self.attention_ln, self.i8x4, self.mlp_stack)
             got = int(nat.lib.lz_policy_blob_format(blob.ctypes.data, blob.size))
             if got != want:
                 raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "policy blob format %d, the launch "
@@ -597,9 +630,10 @@ class _PolicySeam:
     def _launch(self, kind, args, trace=None):
         """Call _LAUNCH's entry point for this policy; returns the frame stack it wrote
         (None unless the family carries one)."""
-        fn = getattr(nat.lib, _LAUNCH[kind, self.family, "fp32" if self.f32 else "bf16"])
+        key = (kind, self.family, "fp32" if self.f32 else "bf16")
+        fn = getattr(nat.lib, _STACK_LAUNCH[key] if key in _STACK_LAUNCH else _LAUNCH[key])
         stack_out, extra = None, ()
-        if self.attention_ln:
+        if self.attention_ln or self.mlp_stack:
             stack_out = torch.empty((self.n, self.frame_stack * self.O), dtype=torch.float32,
                                     device=self.device)
             extra = (self.frame_stack, _p(self.last_stack), _p(stack_out))
@@ -675,6 +709,8 @@ class FusedRolloutCollector(_PolicySeam):
         A state_dict with code/train.py's AttentionFeaturesExtractor selects the
         attention kernel (lz_rollout_policy_attn), any other the MlpPolicy kernel."""
         self._select(state_dict)
+        if self.mlp_stack and self.precision not in (None, "fp32"):
+            raise ValueError("the frame-stacked MlpPolicy rollout runs precision='fp32' only")
         self.f32 = self.precision != "bf16"
         self.i8x4 = self.precision == "i8x4"
         if self.i8x4 and self.family == "mlp":
@@ -724,7 +760,7 @@ class FusedRolloutCollector(_PolicySeam):
             self.reset()
         n, O, A, dev = self.n, self.O, self.A, self.device
         f32 = torch.float32
-        SO = self.frame_stack * O if self.attention_ln else O
+        SO = self.frame_stack * O if (self.attention_ln or self.mlp_stack) else O
         obs_buf = torch.empty((K, n, SO), dtype=f32, device=dev)
         act_buf = torch.empty((K, n, A), dtype=f32, device=dev)
         logp = torch.empty((K, n), dtype=f32, device=dev)
@@ -1001,7 +1037,9 @@ class FusedEvaluator(_PolicySeam):
     obs_rms:       DeviceRunningMeanStd whose statistics stay frozen, or None
     deterministic: SB3 predict(deterministic=True) (default); False draws the Philox
                    normals a rollout would
-    frame_stack:   1 or 4 (VecFrameStack in front of the LayerNorm attention policy)
+    frame_stack:   1 or 4 (VecFrameStack in front of the LayerNorm attention policy, or of
+                   the 64-unit MlpPolicy code/lorenz_filter/train.py:109-131 trains:
+                   lz_stack_evaluate_policy_f32, untraced)
     """
 
     _what = "evaluation"
@@ -1044,6 +1082,8 @@ class FusedEvaluator(_PolicySeam):
         the state planes (the master and slave states).  trace_out / trace_slot_map:
         caller-owned buffers for the rows (float32, >= T * M * C elements) and the launch's
         slot map (int32 [N]); allocated here when None."""
+        if trace is not None and self.mlp_stack:
+            raise ValueError("the frame-stacked MlpPolicy evaluation has no traced form (trace=)")
         if self.last_obs is None:
             self.reset()
         n, O, dev = self.n, self.O, self.device
@@ -1171,10 +1211,20 @@ def net_arch_hidden(net_arch, who="net_arch"):
     return int(arch)
 
 
-def _grad_fns(kind, hidden, O, A, who):
+def _grad_fns(kind, hidden, O, A, who, wide=False):
     """(P, workspace_bytes(n, max_workgroups), grad entry point) for a hidden size: the
-    first entry points at HIDDEN, the _hidden ones (lz_a2c_grad_hidden_f32, ...) otherwise."""
+    first entry points at HIDDEN, the _hidden ones (lz_a2c_grad_hidden_f32, ...) otherwise;
+    wide (PPO only): the _wide ones, the 64-unit net on up to 24 inputs."""
     H = int(hidden)
+    if wide:
+        if kind != "ppo":
+            raise nat.LorenzEnvError(nat.LZ_ERR_UNSUPPORTED, "%s: the wide gradient is PPO's" % who)
+        P = int(nat.lib.lz_ppo_param_count_wide(O, A, H))
+        if P < 0:
+            raise nat.LorenzEnvError(nat.LZ_ERR_UNSUPPORTED, "%s: the wide gradient takes obs_dim "
+                                     "1..24, act_dim 1..4 and hidden 64" % who)
+        ws = nat.lib.lz_ppo_workspace_bytes_wide
+        return P, (lambda n, cap: int(ws(n, O, A, H, cap))), nat.lib.lz_ppo_grad_wide_f32
     if nat.lib.lz_a2c_param_count(O, A) < 0:
         raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "%s: obs_dim must be 1..8, act_dim 1..4" % who)
     if H == HIDDEN:
@@ -1252,6 +1302,9 @@ class _FusedLearner:
     float32 device vector in a2c_param_layout's order, the schedules, and SB3's
     OnPolicyAlgorithm.learn loop around the subclass's per-rollout step."""
 
+    # the frame stack a learner also trains on: FusedPPO's 4 (with net_arch=64), else none
+    _frame_stacks = ()
+
     def __init__(self, collector, state_dict, learning_rate, n_steps, net_arch=None):
         who = type(self).__name__
         # SB3's policy_kwargs["net_arch"]; None: the 128-unit net, as before the 64-unit form
@@ -1262,11 +1315,15 @@ class _FusedLearner:
         if collector.precision in ("bf16", "i8x4"):
             raise ValueError("%s needs a float32 collector (precision='fp32'), not %r"
                              % (who, collector.precision))
-        if collector.frame_stack != 1:
+        # the frame-stacked 64-unit MlpPolicy (code/lorenz_filter/train.py:109-131): the
+        # learner's input is the stacked observation, its gradient the _wide entry points'
+        self.wide = (collector.frame_stack != 1 and collector.frame_stack in self._frame_stacks
+                     and self.hidden == STACK_HIDDEN)
+        if collector.frame_stack != 1 and not self.wide:
             raise ValueError("%s updates the MlpPolicy (frame_stack=1)" % who)
         self.collector = collector
         self.device = collector.device
-        self.O, self.A = collector.O, collector.A
+        self.O, self.A = collector.frame_stack * collector.O, collector.A
         self.layout, self.P = a2c_param_layout(self.O, self.A, self.hidden)
         flat = []
         for k, (_, shp) in self.layout.items():
@@ -1302,7 +1359,7 @@ class _FusedLearner:
 
     def _workspace_need(self, kind, n):
         """Entries of the workspace a gradient launch on n samples needs."""
-        return _grad_fns(kind, self.hidden, self.O, self.A, type(self).__name__)[1](n, 0) // 8
+        return _grad_fns(kind, self.hidden, self.O, self.A, type(self).__name__, self.wide)[1](n, 0) // 8
 
     def _workspace(self, need):
         """The gradient kernels' float64 workspace, grown to `need` entries."""
@@ -1437,8 +1494,10 @@ def ppo_adv_moments(advantages, indices=None, out=None):
 
 def ppo_grad(params, observations, actions, advantages, returns, old_log_prob, old_values, obs_dim,
              act_dim, indices=None, clip_range=0.2, clip_range_vf=None, adv_moments=None, ctrl=None,
-             vf_coef=0.5, ent_coef=0.0, max_workgroups=0, workspace=None, out=None, hidden=HIDDEN):
-    """lz_ppo_grad_f32 (hidden=64: lz_ppo_grad_hidden_f32) on the current stream over the rows `indices` (int32 device tensor
+             vf_coef=0.5, ent_coef=0.0, max_workgroups=0, workspace=None, out=None, hidden=HIDDEN,
+             wide=False):
+    """lz_ppo_grad_f32 (hidden=64: lz_ppo_grad_hidden_f32; wide: lz_ppo_grad_wide_f32, obs_dim up
+    to 24 at hidden=64) on the current stream over the rows `indices` (int32 device tensor
     [M]; None: every row) of the flat rollout arrays: float64 device tensor [P + 6] of the
     gradient sums, then sum(policy loss terms), sum((ret - v_pred)^2), sum(-entropy), M,
     the clipped count and sum((ratio - 1) - log_ratio).  adv_moments: ppo_adv_moments'
@@ -1449,7 +1508,7 @@ def ppo_grad(params, observations, actions, advantages, returns, old_log_prob, o
     O, A = int(obs_dim), int(act_dim)
     if dev.type != "cuda":
         raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "ppo_grad: params must be a device tensor")
-    P, ws_bytes, grad_fn = _grad_fns("ppo", hidden, O, A, "ppo_grad")
+    P, ws_bytes, grad_fn = _grad_fns("ppo", hidden, O, A, "ppo_grad", wide)
     n_rows = int(advantages.numel())
     cvf = 0.0 if clip_range_vf is None else float(clip_range_vf)
     f32 = torch.float32
@@ -1523,7 +1582,12 @@ class FusedPPO(_FusedLearner):
     progress_remaining (linear_schedule).  generator: the torch.Generator (on the
     collector's device) the permutations are drawn from.  net_arch: as FusedA2C's (64 is
     what code/train.py:106-118 and code/lorenz_filter/train.py:117-129 train, and the size of
-    the reference's shipped PPO policies).  Float32 MlpPolicy collectors only."""
+    the reference's shipped PPO policies).  Float32 MlpPolicy collectors only -- with
+    net_arch=64 also the frame-stacked one (frame_stack=4: code/lorenz_filter/train.py:109-131's
+    PPO("MlpPolicy") on VecFrameStack(n_stack=4)), through lz_ppo_grad_wide_f32 on the
+    stacked observations."""
+
+    _frame_stacks = (4,)
 
     def __init__(self, collector, state_dict, learning_rate=3e-4, n_steps=2048, batch_size=64,
                  n_epochs=10, clip_range=0.2, clip_range_vf=None, normalize_advantage=True,
@@ -1614,7 +1678,7 @@ class FusedPPO(_FusedLearner):
         ppo_grad(self.params, batch.observations, batch.actions, batch.advantages, batch.returns,
                  batch.log_probs, batch.values, self.O, self.A, indices, clip_range, clip_range_vf, mom,
                  self.ctrl, self.vf_coef, self.ent_coef, workspace=self._ws, out=self._sums,
-                 hidden=self.hidden)
+                 hidden=self.hidden, wide=self.wide)
         adam_apply(self._sums, self.params, self.exp_avg, self.exp_avg_sq, self.ctrl, lr,
                    self.max_grad_norm, (0.9, 0.999), 1e-5, self.vf_coef, self.ent_coef, self.target_kl,
                    stats=stats_row)

@@ -389,7 +389,8 @@ enum {
   LZ_BLOB_ATTN_F32 = 3,      /* lz_attn_policy_pack_f32 */
   LZ_BLOB_ATTN_I8X4 = 4,     /* lz_attn_policy_pack_i8x4 */
   LZ_BLOB_ATTN_LN_F32 = 5,   /* lz_attn_ln_policy_pack_f32 */
-  LZ_BLOB_ATTN_LN_I8X4 = 6   /* lz_attn_ln_policy_pack_i8x4 */
+  LZ_BLOB_ATTN_LN_I8X4 = 6,  /* lz_attn_ln_policy_pack_i8x4 */
+  LZ_BLOB_MLP_STACK_F32 = 7  /* lz_policy_pack_stack_f32 */
 };
 /* The LZ_BLOB_* format of a packed host blob of `size` bytes (LZ_BLOB_UNKNOWN: not a
  * tagged float32 / i8x4 blob, or too small).  Host-only; lets a C-ABI caller check a blob
@@ -436,6 +437,23 @@ lz_status lz_policy_pack_hidden(const lz_mlp_policy* p, int32_t hidden, void* ho
  * for bit by the C oracle.  hidden 1..128 as lz_policy_pack_hidden.  Host-only. */
 int64_t lz_policy_f32_blob_bytes(void);
 lz_status lz_policy_pack_f32(const lz_mlp_policy* p, int32_t hidden, void* host_blob, int64_t cap);
+
+/* The float32 MlpPolicy on VecFrameStack(n_stack = 4) observations, the policy
+ * code/lorenz_filter/train.py:109-131 trains (its policy_kwargs are never passed on, so
+ * SB3's default net_arch [64, 64] Tanh runs on the 24-wide stacked observation): a native
+ * 64-unit blob -- two 32-unit output tiles per layer, 12 layer-1 k-steps -- because the
+ * 128-unit float32 blob widened to 24 inputs would not fit a workgroup's LDS.  obs_dim
+ * (the stacked input width) 1..24, zero-padded to 24; act_dim 1..4; hidden must be 64
+ * (else LZ_ERR_UNSUPPORTED).  Per net: W1 [2 tiles][64 lanes][12 k-steps] f32 (lane
+ * (r, h), k-step s: W1[32t + r][2s + h]), W2 [2][8 quads][64 lanes][4] (k-step q = 4 quad
+ * + e: input unit 32 (q >> 4) + row(q & 15, h), row(g, h) = (g & 3) + 8 (g >> 2) + 4 h),
+ * b1 / b2 [2][2 halves][16] as accumulator initialisers (tile t register g of half h =
+ * unit 32t + row(g, h)), head rows [4][2 halves][32] (element 16t + g), head bias [4];
+ * then the 16 Normal constants and the tanh table as lz_policy_pack_f32.  Tag
+ * LZ_BLOB_MLP_STACK_F32.  Host-only. */
+int64_t lz_policy_stack_f32_blob_bytes(void);
+lz_status lz_policy_pack_stack_f32(const lz_mlp_policy* p, int32_t hidden, void* host_blob,
+                                   int64_t cap);
 
 typedef struct lz_policy_rollout_args {
   int32_t K;                /* steps (SB3 n_steps) */
@@ -612,6 +630,15 @@ lz_status lz_attn_ln_policy_pack_i8x4(const lz_attn_ln_policy* p, void* host_blo
 lz_status lz_rollout_policy_attn_stack_f32(lz_handle* h, const lz_policy_rollout_args* r,
                                            int32_t n_stack, const float* stack_in,
                                            float* stack_out);
+/* The rollout of an lz_policy_pack_stack_f32 blob (code/lorenz_filter/train.py:109-131:
+ * PPO("MlpPolicy") on VecFrameStack(n_stack=4)): lz_rollout_policy_attn_stack_f32's
+ * contract with the 64-unit MlpPolicy as the actor-critic -- obs_buf is [K, N, 4 O], the
+ * stacked observation the policy saw; stack_in / stack_out [N, 4 O] carry the stack; the
+ * truncation bootstrap values the stacked terminal observation.  n_stack must be 4;
+ * LORENZ3 / PMSM / HR, float32 Euler handles; no VecNormalize statistics, no
+ * LZ_POLICY_I8X4.  A blob of another format gives all-NaN outputs. */
+lz_status lz_stack_rollout_policy_f32(lz_handle* h, const lz_policy_rollout_args* r,
+                                      int32_t n_stack, const float* stack_in, float* stack_out);
 
 /* ------------------------------------------------------------------------------
  * Fused policy evaluation.  What the reference does with a trained policy: a closed loop
@@ -697,6 +724,11 @@ lz_status lz_evaluate_policy_attn_f32(lz_handle* h, const lz_policy_eval_args* e
 lz_status lz_evaluate_policy_attn_stack_f32(lz_handle* h, const lz_policy_eval_args* e,
                                             int32_t n_stack, const float* stack_in,
                                             float* stack_out);
+/* ... of an lz_policy_pack_stack_f32 blob (code/lorenz_filter/test_evaluate.py:94-157
+ * evaluates the frame-stacked MlpPolicy): the pi net only, n_stack must be 4, the same
+ * table.  There is no traced form. */
+lz_status lz_stack_evaluate_policy_f32(lz_handle* h, const lz_policy_eval_args* e, int32_t n_stack,
+                                       const float* stack_in, float* stack_out);
 
 /* ------------------------------------------------------------------------------
  * Per-step trajectories of chosen envs in the fused evaluation.  Every one of the
@@ -1000,6 +1032,21 @@ int64_t lz_ppo_workspace_bytes_hidden(int64_t n_samples, int32_t obs_dim, int32_
                                       int32_t hidden, int32_t max_workgroups);
 lz_status lz_ppo_grad_hidden_f32(const lz_ppo_grad_args* g, int32_t device, void* hip_stream);
 
+/* The same minibatch gradient for the 64-unit MlpPolicy on a frame-stacked observation,
+ * the net code/lorenz_filter/train.py:109-131 trains (PPO("MlpPolicy") on
+ * VecFrameStack(n_stack=4): tensors (64, 24) / (64, 64) / (A, 64), P = 11,717 at obs_dim
+ * 24, act_dim 2): obs_dim 1..24, act_dim 1..4, hidden == 64 only (anything else is
+ * LZ_ERR_UNSUPPORTED, after the dims check; the count and the workspace function return -1).
+ * obs_dim <= 8 launches lz_ppo_grad_hidden_f32's 64-unit kernel (the same bits), a wider
+ * one k_ppo_grad_h64_wide: the same text with 24-wide x and W1 images and 12 layer-1 MFMA
+ * steps.  params is [lz_ppo_param_count_wide], grad_sums [that + 6]; grid rule, flush
+ * period, ctrl, lz_ppo_adv_moments and lz_adam_apply_f32 as above; every other refusal is
+ * lz_ppo_grad_hidden_f32's, in its order. */
+int64_t lz_ppo_param_count_wide(int32_t obs_dim, int32_t act_dim, int32_t hidden);
+int64_t lz_ppo_workspace_bytes_wide(int64_t n_samples, int32_t obs_dim, int32_t act_dim,
+                                    int32_t hidden, int32_t max_workgroups);
+lz_status lz_ppo_grad_wide_f32(const lz_ppo_grad_args* g, int32_t device, void* hip_stream);
+
 /* RolloutBuffer.episode_starts of one collect (SB3 2.7.1 OnPolicyAlgorithm.
  * collect_rollouts: rollout_buffer.add(..., self._last_episode_starts, ...), then
  * _last_episode_starts = dones): starts[0] = last_in, starts[k] = (done[k-1] != 0)
@@ -1165,7 +1212,11 @@ enum {
                                               k_step: the multi-tile kernel draws on device) */
   LZ_CALL_EVALUATE_POLICY_F32 = 10,        /* lz_evaluate_policy_f32 */
   LZ_CALL_EVALUATE_POLICY_ATTN_F32 = 11,   /* lz_evaluate_policy_attn_f32 */
-  LZ_CALL_EVALUATE_POLICY_ATTN_STACK_F32 = 12 /* lz_evaluate_policy_attn_stack_f32 */
+  LZ_CALL_EVALUATE_POLICY_ATTN_STACK_F32 = 12, /* lz_evaluate_policy_attn_stack_f32 */
+  LZ_CALL_ROLLOUT_POLICY_STACK_F32 = 13,   /* lz_stack_rollout_policy_f32
+                                              (code/lorenz_filter/train.py:109-131) */
+  LZ_CALL_EVALUATE_POLICY_STACK_F32 = 14   /* lz_stack_evaluate_policy_f32
+                                              (code/lorenz_filter/test_evaluate.py:94-157) */
 };
 enum {
   LZ_KERNEL_STEP = 1,             /* k_step: one 256-env tile per workgroup */
@@ -1183,7 +1234,11 @@ enum {
   LZ_KERNEL_ROLLOUT_PAIR = 13,    /* k_rollout_pair: PMSM, the step split over a lane
                                      pair (SysPMSM::step_pair) */
   LZ_KERNEL_EVAL = 14,            /* k_evaluate_policy_f32: one wave per 32-env tile, pi net only */
-  LZ_KERNEL_EVAL_ATTN_F32 = 15    /* k_evaluate_policy_attn_f32: 16-env waves, pi net resident */
+  LZ_KERNEL_EVAL_ATTN_F32 = 15,   /* k_evaluate_policy_attn_f32: 16-env waves, pi net resident */
+  LZ_KERNEL_POLICY_STACK_F32 = 16, /* k_rollout_policy_stack_f32: 64-unit MlpPolicy on the frame
+                                      stack (code/lorenz_filter/train.py:109-131) */
+  LZ_KERNEL_EVAL_STACK_F32 = 17   /* k_evaluate_policy_stack_f32
+                                     (code/lorenz_filter/test_evaluate.py:94-157) */
 };
 #define LZ_SHAPE_NO_DONE 1u     /* the done-free instantiation (no done can occur) */
 #define LZ_SHAPE_GRID_STRIDE 2u /* fewer workgroups than env groups: workgroups loop */
