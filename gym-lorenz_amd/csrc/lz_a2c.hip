@@ -19,10 +19,8 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
 
 #include "lz_grad_common.h"
-#include "lz_internal.h"
 
 namespace lz {
 namespace a2c {
@@ -57,6 +55,11 @@ struct GradArgs {
 #undef LZ_GRAD_KERNEL
 #undef LZ_GRAD_H
 #undef LZ_GRAD_PPO
+
+// the forms above and the two entry points' rules
+constexpr Form<GradArgs> kForms[] = {{kH, kMaxO, 2 * kH, k_a2c_grad}, {kH64, kMaxO, 2 * kH64, k_a2c_grad_h64}};
+constexpr Rule kGrad = {"lz_a2c_grad_f32", "lz_a2c_workspace_bytes", kMaxO, kH, kH};
+constexpr Rule kGradHidden = {"lz_a2c_grad_hidden_f32", "lz_a2c_workspace_bytes_hidden", kMaxO, kH64, kH};
 
 // out[i] = the slots' entries i added in slot order
 __global__ __launch_bounds__(256) void k_a2c_reduce(const double* __restrict__ part, int nwg,
@@ -120,103 +123,64 @@ __global__ __launch_bounds__(1024) void k_a2c_apply(ApplyArgs a) {
 }  // namespace a2c
 }  // namespace lz
 
+using namespace lz::a2c;  // the entry points below
+
 extern "C" int64_t lz_a2c_param_count(int32_t obs_dim, int32_t act_dim) {
-  if (!lz::a2c::dims_ok(obs_dim, act_dim)) return -1;
-  return lz::a2c::layout(obs_dim, act_dim).P;
+  return param_count(kGrad, obs_dim, act_dim, kH);
 }
 
 extern "C" int64_t lz_a2c_workspace_bytes(int64_t n_samples, int32_t obs_dim, int32_t act_dim,
                                           int32_t max_workgroups) {
-  if (!lz::a2c::dims_ok(obs_dim, act_dim) || n_samples < 1 || max_workgroups < 0 ||
-      max_workgroups > lz::a2c::kMaxWgs)
-    return -1;
-  const int64_t P = lz::a2c::layout(obs_dim, act_dim).P;
-  return (int64_t)lz::a2c::wgs_per_net(n_samples, max_workgroups) * (P + 4) * (int64_t)sizeof(double);
+  return workspace_bytes(kGrad, n_samples, obs_dim, act_dim, kH, max_workgroups, kTail);
 }
 
 extern "C" int64_t lz_a2c_param_count_hidden(int32_t obs_dim, int32_t act_dim, int32_t hidden) {
-  if (!lz::a2c::dims_ok(obs_dim, act_dim) || !lz::a2c::hidden_ok(hidden)) return -1;
-  return lz::a2c::layout(obs_dim, act_dim, hidden).P;
+  return param_count(kGradHidden, obs_dim, act_dim, hidden);
 }
 
 extern "C" int64_t lz_a2c_workspace_bytes_hidden(int64_t n_samples, int32_t obs_dim, int32_t act_dim,
                                                  int32_t hidden, int32_t max_workgroups) {
-  using namespace lz::a2c;
-  if (!dims_ok(obs_dim, act_dim) || !hidden_ok(hidden) || n_samples < 1 || max_workgroups < 0 ||
-      max_workgroups > kMaxWgs)
-    return -1;
-  const int64_t P = layout(obs_dim, act_dim, hidden).P;
-  return (int64_t)wgs_per_net(n_samples, max_workgroups) * (P + kTail) * (int64_t)sizeof(double);
+  return workspace_bytes(kGradHidden, n_samples, obs_dim, act_dim, hidden, max_workgroups, kTail);
 }
 
 namespace {
 
-lz_status fail(lz_status s, const char* who, const char* what) {
-  char m[160];
-  snprintf(m, sizeof m, "%s: %s", who, what);
-  return lz::set_error(s, m);
-}
-
-// lz_a2c_grad_f32 (any_hidden false: 128 units only) and lz_a2c_grad_hidden_f32: the same
-// refusals in the same order, then the launch of the form built for g->hidden
-lz_status grad_entry(const lz_a2c_grad_args* g, int32_t device, void* stream, const char* who,
-                     bool any_hidden) {
-  using namespace lz::a2c;
-  if (!g) return fail(LZ_ERR_INVALID, who, "NULL args");
+// every A2C gradient entry point: the refusals in Rule's order, then the launch of the form
+// built for g->hidden
+lz_status grad_entry(const Rule& r, const lz_a2c_grad_args* g, int32_t device, void* stream) {
+  if (!g) return fail(LZ_ERR_INVALID, r.who, "NULL args");
   if (!g->params || !g->observations || !g->actions || !g->advantages || !g->returns ||
       !g->workspace || !g->grad_sums)
-    return fail(LZ_ERR_INVALID, who, "NULL buffer");
-  if (!dims_ok(g->obs_dim, g->act_dim))
-    return fail(LZ_ERR_INVALID, who, "obs_dim must be 1..8 and act_dim 1..4");
-  if (g->n_samples < 1) return fail(LZ_ERR_INVALID, who, "n_samples < 1");
-  if (g->max_workgroups < 0 || g->max_workgroups > kMaxWgs)
-    return fail(LZ_ERR_INVALID, who, "max_workgroups must be 0..4096");
-  if (any_hidden ? !hidden_ok(g->hidden) : g->hidden != kH)
-    return fail(LZ_ERR_UNSUPPORTED, who, any_hidden ? "hidden must be 64 or 128" : "hidden must be 128");
-  const int64_t need = lz_a2c_workspace_bytes_hidden(g->n_samples, g->obs_dim, g->act_dim, g->hidden,
-                                                     g->max_workgroups);
-  if (g->workspace_bytes < need)
-    return fail(LZ_ERR_INVALID, who, any_hidden ? "workspace smaller than lz_a2c_workspace_bytes_hidden"
-                                                : "workspace smaller than lz_a2c_workspace_bytes");
+    return fail(LZ_ERR_INVALID, r.who, "NULL buffer");
+  if (lz_status e = check_shape(r, g->obs_dim, g->act_dim, g->n_samples)) return e;
+  if (lz_status e = check_launch(r, g->n_samples, g->obs_dim, g->act_dim, g->hidden, g->max_workgroups,
+                                 kTail, g->workspace_bytes))
+    return e;
+  const Form<GradArgs>* form = pick_form(kForms, g->hidden, g->obs_dim);
+  if (!form) return fail(LZ_ERR_UNSUPPORTED, r.who, "no kernel is built for this net");
   if (hipSetDevice(device) != hipSuccess) return lz::set_error(LZ_ERR_HIP, "hipSetDevice failed");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nwg = wgs_per_net(g->n_samples, g->max_workgroups);
   const int64_t len = layout(g->obs_dim, g->act_dim, g->hidden).P + kTail;
   GradArgs a;
-  a.params = g->params;
-  a.obs = g->observations;
-  a.act = g->actions;
-  a.adv = g->advantages;
-  a.ret = g->returns;
-  a.n = g->n_samples;
-  a.O = g->obs_dim;
-  a.A = g->act_dim;
-  a.vf_coef = (float)g->vf_coef;
-  a.ent_coef = (float)g->ent_coef;
-  a.part = static_cast<double*>(g->workspace);
-  if (g->hidden == kH64)
-    hipLaunchKernelGGL(k_a2c_grad_h64, dim3(2u * (unsigned)nwg), dim3(2 * kH64), 0, s, a);
-  else
-    hipLaunchKernelGGL(k_a2c_grad, dim3(2u * (unsigned)nwg), dim3(2 * kH), 0, s, a);
+  common_args(a, *g);
+  hipLaunchKernelGGL(form->kernel, dim3(2u * (unsigned)nwg), dim3(form->threads), 0, s, a);
   hipLaunchKernelGGL(k_a2c_reduce, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s,
                      static_cast<const double*>(g->workspace), nwg, len, g->grad_sums);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return lz::set_error(LZ_ERR_HIP, hipGetErrorString(e));
-  return LZ_OK;
+  return launched();
 }
 
 }  // namespace
 
 extern "C" lz_status lz_a2c_grad_f32(const lz_a2c_grad_args* g, int32_t device, void* stream) {
-  return grad_entry(g, device, stream, "lz_a2c_grad_f32", false);
+  return grad_entry(kGrad, g, device, stream);
 }
 
 extern "C" lz_status lz_a2c_grad_hidden_f32(const lz_a2c_grad_args* g, int32_t device, void* stream) {
-  return grad_entry(g, device, stream, "lz_a2c_grad_hidden_f32", true);
+  return grad_entry(kGradHidden, g, device, stream);
 }
 
 extern "C" lz_status lz_a2c_apply_f32(const lz_a2c_apply_args* p, int32_t device, void* stream) {
-  using namespace lz::a2c;
   if (!p) return lz::set_error(LZ_ERR_INVALID, "lz_a2c_apply_f32: NULL args");
   if (!p->grad_sums || !p->params || !p->square_avg || !p->stats)
     return lz::set_error(LZ_ERR_INVALID, "lz_a2c_apply_f32: NULL buffer");
@@ -235,7 +199,5 @@ extern "C" lz_status lz_a2c_apply_f32(const lz_a2c_apply_args* p, int32_t device
   a.ent_coef = p->ent_coef;
   a.stats = p->stats;
   hipLaunchKernelGGL(k_a2c_apply, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return lz::set_error(LZ_ERR_HIP, hipGetErrorString(e));
-  return LZ_OK;
+  return launched();
 }

@@ -46,10 +46,8 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
 
 #include "lz_grad_common.h"
-#include "lz_internal.h"
 
 namespace lz {
 namespace ppo {
@@ -103,8 +101,14 @@ struct GradArgs {
 #undef LZ_GRAD_H
 #undef LZ_GRAD_PPO
 
-constexpr int kWideMaxO = 24;  // LZ_GRAD_MAXO of k_ppo_grad_h64_wide
-inline bool wide_dims_ok(int O, int A) { return O >= 1 && O <= kWideMaxO && A >= 1 && A <= kMaxA; }
+// the forms above (the wide one after the narrow one it falls back to at obs_dim <= 8) and
+// the three entry points' rules (24: the wide form's LZ_GRAD_MAXO, the wide rule's limit)
+constexpr Form<GradArgs> kForms[] = {{kH, kMaxO, 2 * kH, k_ppo_grad},
+                                     {kH64, kMaxO, 2 * kH64, k_ppo_grad_h64},
+                                     {kH64, 24, 2 * kH64, k_ppo_grad_h64_wide}};
+constexpr Rule kGrad = {"lz_ppo_grad_f32", "lz_ppo_workspace_bytes", kMaxO, kH, kH};
+constexpr Rule kGradHidden = {"lz_ppo_grad_hidden_f32", "lz_ppo_workspace_bytes_hidden", kMaxO, kH64, kH};
+constexpr Rule kGradWide = {"lz_ppo_grad_wide_f32", "lz_ppo_workspace_bytes_wide", kForms[2].max_obs, kH64, kH64};
 
 // out[i] = the slots' entries i added in slot order (nothing after the stop, as k_ppo_grad)
 __global__ __launch_bounds__(256) void k_ppo_reduce(const double* __restrict__ part, int nwg,
@@ -254,45 +258,30 @@ __global__ __launch_bounds__(1024) void k_adam_apply(AdamArgs a) {
 }  // namespace ppo
 }  // namespace lz
 
+using namespace lz::ppo;  // the entry points below
+
 extern "C" int64_t lz_ppo_workspace_bytes(int64_t n_samples, int32_t obs_dim, int32_t act_dim,
                                           int32_t max_workgroups) {
-  using namespace lz::ppo;
-  if (!dims_ok(obs_dim, act_dim) || n_samples < 1 || max_workgroups < 0 || max_workgroups > kMaxWgs)
-    return -1;
-  const int64_t P = layout(obs_dim, act_dim).P;
-  return (int64_t)wgs_per_net(n_samples, max_workgroups) * (P + kTail) * (int64_t)sizeof(double);
+  return workspace_bytes(kGrad, n_samples, obs_dim, act_dim, kH, max_workgroups, kTail);
 }
 
 extern "C" int64_t lz_ppo_workspace_bytes_hidden(int64_t n_samples, int32_t obs_dim, int32_t act_dim,
                                                  int32_t hidden, int32_t max_workgroups) {
-  using namespace lz::ppo;
-  if (!dims_ok(obs_dim, act_dim) || !hidden_ok(hidden) || n_samples < 1 || max_workgroups < 0 ||
-      max_workgroups > kMaxWgs)
-    return -1;
-  const int64_t P = layout(obs_dim, act_dim, hidden).P;
-  return (int64_t)wgs_per_net(n_samples, max_workgroups) * (P + kTail) * (int64_t)sizeof(double);
+  return workspace_bytes(kGradHidden, n_samples, obs_dim, act_dim, hidden, max_workgroups, kTail);
 }
 
 extern "C" int64_t lz_ppo_param_count_wide(int32_t obs_dim, int32_t act_dim, int32_t hidden) {
-  using namespace lz::ppo;
-  if (!wide_dims_ok(obs_dim, act_dim) || hidden != kH64) return -1;
-  return layout(obs_dim, act_dim, hidden).P;
+  return param_count(kGradWide, obs_dim, act_dim, hidden);
 }
 
 extern "C" int64_t lz_ppo_workspace_bytes_wide(int64_t n_samples, int32_t obs_dim, int32_t act_dim,
                                                int32_t hidden, int32_t max_workgroups) {
-  using namespace lz::ppo;
-  if (!wide_dims_ok(obs_dim, act_dim) || hidden != kH64 || n_samples < 1 || max_workgroups < 0 ||
-      max_workgroups > kMaxWgs)
-    return -1;
-  const int64_t P = layout(obs_dim, act_dim, hidden).P;
-  return (int64_t)wgs_per_net(n_samples, max_workgroups) * (P + kTail) * (int64_t)sizeof(double);
+  return workspace_bytes(kGradWide, n_samples, obs_dim, act_dim, hidden, max_workgroups, kTail);
 }
 
 extern "C" lz_status lz_ppo_adv_moments(const float* advantages, const int32_t* indices,
                                         int64_t n_samples, int64_t n_rows, void* workspace,
                                         double* out, int32_t device, void* stream) {
-  using namespace lz::ppo;
   (void)workspace;
   if (!advantages || !out) return lz::set_error(LZ_ERR_INVALID, "lz_ppo_adv_moments: NULL buffer");
   if (n_samples < 1) return lz::set_error(LZ_ERR_INVALID, "lz_ppo_adv_moments: n_samples < 1");
@@ -302,112 +291,71 @@ extern "C" lz_status lz_ppo_adv_moments(const float* advantages, const int32_t* 
   if (hipSetDevice(device) != hipSuccess) return lz::set_error(LZ_ERR_HIP, "hipSetDevice failed");
   hipLaunchKernelGGL(k_ppo_adv_moments, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream),
                      advantages, indices, n_samples, n_rows, out);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return lz::set_error(LZ_ERR_HIP, hipGetErrorString(e));
-  return LZ_OK;
+  return launched();
 }
 
 namespace {
 
-lz_status fail(lz_status s, const char* who, const char* what) {
-  char m[160];
-  snprintf(m, sizeof m, "%s: %s", who, what);
-  return lz::set_error(s, m);
-}
-
-// lz_ppo_grad_f32 (any_hidden false: 128 units only), lz_ppo_grad_hidden_f32 and
-// lz_ppo_grad_wide_f32 (wide: obs_dim up to 24, 64 units only): the same refusals in the
-// same order, then the launch of the form built for g->hidden (and, wide, g->obs_dim)
-lz_status grad_entry(const lz_ppo_grad_args* g, int32_t device, void* stream, const char* who,
-                     bool any_hidden, bool wide = false) {
-  using namespace lz::ppo;
-  if (!g) return fail(LZ_ERR_INVALID, who, "NULL args");
+// every PPO gradient entry point: the refusals in Rule's order, then the launch of the form
+// built for g->hidden and g->obs_dim
+lz_status grad_entry(const Rule& r, const lz_ppo_grad_args* g, int32_t device, void* stream) {
+  if (!g) return fail(LZ_ERR_INVALID, r.who, "NULL args");
   if (!g->params || !g->observations || !g->actions || !g->advantages || !g->returns ||
       !g->old_log_prob || !g->workspace || !g->grad_sums)
-    return fail(LZ_ERR_INVALID, who, "NULL buffer");
+    return fail(LZ_ERR_INVALID, r.who, "NULL buffer");
   if (g->clip_range_vf > 0.0 && !g->old_values)
-    return fail(LZ_ERR_INVALID, who, "NULL old_values with clip_range_vf > 0");
-  if (wide ? !wide_dims_ok(g->obs_dim, g->act_dim) : !dims_ok(g->obs_dim, g->act_dim))
-    return fail(LZ_ERR_INVALID, who, wide ? "obs_dim must be 1..24 and act_dim 1..4"
-                                          : "obs_dim must be 1..8 and act_dim 1..4");
-  if (g->n_samples < 1) return fail(LZ_ERR_INVALID, who, "n_samples < 1");
-  if (g->n_rows < 1) return fail(LZ_ERR_INVALID, who, "n_rows < 1");
+    return fail(LZ_ERR_INVALID, r.who, "NULL old_values with clip_range_vf > 0");
+  if (lz_status e = check_shape(r, g->obs_dim, g->act_dim, g->n_samples)) return e;
+  if (g->n_rows < 1) return fail(LZ_ERR_INVALID, r.who, "n_rows < 1");
   if (!g->indices && g->n_samples > g->n_rows)
-    return fail(LZ_ERR_INVALID, who, "n_samples > n_rows without indices");
+    return fail(LZ_ERR_INVALID, r.who, "n_samples > n_rows without indices");
   if (!(g->clip_range >= 0.0) || std::isinf(g->clip_range))
-    return fail(LZ_ERR_INVALID, who, "clip_range must be finite and >= 0");
+    return fail(LZ_ERR_INVALID, r.who, "clip_range must be finite and >= 0");
   if (g->clip_range_vf != g->clip_range_vf || std::isinf(g->clip_range_vf))
-    return fail(LZ_ERR_INVALID, who, "clip_range_vf must be finite");
-  if (g->max_workgroups < 0 || g->max_workgroups > kMaxWgs)
-    return fail(LZ_ERR_INVALID, who, "max_workgroups must be 0..4096");
-  if (wide ? g->hidden != kH64 : any_hidden ? !hidden_ok(g->hidden) : g->hidden != kH)
-    return fail(LZ_ERR_UNSUPPORTED, who, wide         ? "hidden must be 64"
-                                         : any_hidden ? "hidden must be 64 or 128"
-                                                      : "hidden must be 128");
-  const int64_t need =
-      wide ? lz_ppo_workspace_bytes_wide(g->n_samples, g->obs_dim, g->act_dim, g->hidden, g->max_workgroups)
-           : lz_ppo_workspace_bytes_hidden(g->n_samples, g->obs_dim, g->act_dim, g->hidden,
-                                           g->max_workgroups);
-  if (g->workspace_bytes < need)
-    return fail(LZ_ERR_INVALID, who, wide         ? "workspace smaller than lz_ppo_workspace_bytes_wide"
-                                     : any_hidden ? "workspace smaller than lz_ppo_workspace_bytes_hidden"
-                                                  : "workspace smaller than lz_ppo_workspace_bytes");
+    return fail(LZ_ERR_INVALID, r.who, "clip_range_vf must be finite");
+  if (lz_status e = check_launch(r, g->n_samples, g->obs_dim, g->act_dim, g->hidden, g->max_workgroups,
+                                 kTail, g->workspace_bytes))
+    return e;
+  const Form<GradArgs>* form = pick_form(kForms, g->hidden, g->obs_dim);
+  if (!form) return fail(LZ_ERR_UNSUPPORTED, r.who, "no kernel is built for this net");
   if (hipSetDevice(device) != hipSuccess) return lz::set_error(LZ_ERR_HIP, "hipSetDevice failed");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nwg = wgs_per_net(g->n_samples, g->max_workgroups);
   const int64_t len = layout(g->obs_dim, g->act_dim, g->hidden).P + kTail;
   GradArgs a;
-  a.params = g->params;
-  a.obs = g->observations;
-  a.act = g->actions;
-  a.adv = g->advantages;
-  a.ret = g->returns;
+  common_args(a, *g);
   a.old_logp = g->old_log_prob;
   a.old_val = g->clip_range_vf > 0.0 ? g->old_values : nullptr;
   a.idx = g->indices;
   a.moments = g->adv_moments;
   a.ctrl = g->ctrl;
-  a.n = g->n_samples;
   a.n_rows = g->n_rows;
-  a.O = g->obs_dim;
-  a.A = g->act_dim;
-  a.vf_coef = (float)g->vf_coef;
-  a.ent_coef = (float)g->ent_coef;
   // torch compares and clamps the float32 ratio with the Python floats rounded to float32
   a.clip = (float)g->clip_range;
   a.clip_lo = (float)(1.0 - g->clip_range);
   a.clip_hi = (float)(1.0 + g->clip_range);
   a.clip_vf = (float)g->clip_range_vf;
-  a.part = static_cast<double*>(g->workspace);
-  if (g->hidden == kH64 && g->obs_dim > kMaxO)  // wide only: the others refused it above
-    hipLaunchKernelGGL(k_ppo_grad_h64_wide, dim3(2u * (unsigned)nwg), dim3(2 * kH64), 0, s, a);
-  else if (g->hidden == kH64)
-    hipLaunchKernelGGL(k_ppo_grad_h64, dim3(2u * (unsigned)nwg), dim3(2 * kH64), 0, s, a);
-  else
-    hipLaunchKernelGGL(k_ppo_grad, dim3(2u * (unsigned)nwg), dim3(2 * kH), 0, s, a);
+  hipLaunchKernelGGL(form->kernel, dim3(2u * (unsigned)nwg), dim3(form->threads), 0, s, a);
   hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s,
                      static_cast<const double*>(g->workspace), nwg, len, g->ctrl, g->grad_sums);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return lz::set_error(LZ_ERR_HIP, hipGetErrorString(e));
-  return LZ_OK;
+  return launched();
 }
 
 }  // namespace
 
 extern "C" lz_status lz_ppo_grad_f32(const lz_ppo_grad_args* g, int32_t device, void* stream) {
-  return grad_entry(g, device, stream, "lz_ppo_grad_f32", false);
+  return grad_entry(kGrad, g, device, stream);
 }
 
 extern "C" lz_status lz_ppo_grad_hidden_f32(const lz_ppo_grad_args* g, int32_t device, void* stream) {
-  return grad_entry(g, device, stream, "lz_ppo_grad_hidden_f32", true);
+  return grad_entry(kGradHidden, g, device, stream);
 }
 
 extern "C" lz_status lz_ppo_grad_wide_f32(const lz_ppo_grad_args* g, int32_t device, void* stream) {
-  return grad_entry(g, device, stream, "lz_ppo_grad_wide_f32", true, true);
+  return grad_entry(kGradWide, g, device, stream);
 }
 
 extern "C" lz_status lz_adam_apply_f32(const lz_adam_apply_args* p, int32_t device, void* stream) {
-  using namespace lz::ppo;
   if (!p) return lz::set_error(LZ_ERR_INVALID, "lz_adam_apply_f32: NULL args");
   if (!p->grad_sums || !p->params || !p->exp_avg || !p->exp_avg_sq || !p->ctrl || !p->stats)
     return lz::set_error(LZ_ERR_INVALID, "lz_adam_apply_f32: NULL buffer");
@@ -432,7 +380,5 @@ extern "C" lz_status lz_adam_apply_f32(const lz_adam_apply_args* p, int32_t devi
   a.ctrl = p->ctrl;
   a.stats = p->stats;
   hipLaunchKernelGGL(k_adam_apply, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return lz::set_error(LZ_ERR_HIP, hipGetErrorString(e));
-  return LZ_OK;
+  return launched();
 }

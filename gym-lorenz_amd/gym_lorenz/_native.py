@@ -393,28 +393,10 @@ _SIGS = {
                                                                ctypes.POINTER(LzEvalTrace)]),
     "lz_gae": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, VP, VP, VP, VP, ctypes.c_double,
                               ctypes.c_double, VP, VP, ctypes.c_int32, VP]),
-    "lz_a2c_param_count": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
-    "lz_a2c_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_int32]),
-    "lz_a2c_grad_f32": (ctypes.c_int, [ctypes.POINTER(LzA2cGradArgs), ctypes.c_int32, VP]),
     "lz_a2c_apply_f32": (ctypes.c_int, [ctypes.POINTER(LzA2cApplyArgs), ctypes.c_int32, VP]),
-    "lz_ppo_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_int32]),
     "lz_ppo_adv_moments": (ctypes.c_int, [VP, VP, ctypes.c_int64, ctypes.c_int64, VP, VP,
                                           ctypes.c_int32, VP]),
-    "lz_ppo_grad_f32": (ctypes.c_int, [ctypes.POINTER(LzPpoGradArgs), ctypes.c_int32, VP]),
     "lz_adam_apply_f32": (ctypes.c_int, [ctypes.POINTER(LzAdamApplyArgs), ctypes.c_int32, VP]),
-    "lz_a2c_param_count_hidden": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "lz_a2c_workspace_bytes_hidden": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                       ctypes.c_int32, ctypes.c_int32]),
-    "lz_a2c_grad_hidden_f32": (ctypes.c_int, [ctypes.POINTER(LzA2cGradArgs), ctypes.c_int32, VP]),
-    "lz_ppo_workspace_bytes_hidden": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                       ctypes.c_int32, ctypes.c_int32]),
-    "lz_ppo_grad_hidden_f32": (ctypes.c_int, [ctypes.POINTER(LzPpoGradArgs), ctypes.c_int32, VP]),
-    "lz_ppo_param_count_wide": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "lz_ppo_workspace_bytes_wide": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                     ctypes.c_int32, ctypes.c_int32]),
-    "lz_ppo_grad_wide_f32": (ctypes.c_int, [ctypes.POINTER(LzPpoGradArgs), ctypes.c_int32, VP]),
     "lz_episode_starts": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, VP, VP, VP, VP,
                                          ctypes.c_int32, VP]),
     "lz_frame_stack": (ctypes.c_int, [VP, VP, VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
@@ -423,6 +405,25 @@ _SIGS = {
     "lz_last_error": (ctypes.c_char_p, []),
     "lz_abi_version": (ctypes.c_int32, []),
 }
+
+# The gradient entry points by (learner, generation): the parameter count, the workspace size
+# and the gradient function, and whether the first two take `hidden` (csrc/lz_grad_common.h's
+# rules are the native side of these rows).  PPO counts with A2C's functions: the same vector.
+GRAD_ENTRIES = {
+    ("a2c", "first"): ("lz_a2c_param_count", "lz_a2c_workspace_bytes", "lz_a2c_grad_f32", False),
+    ("ppo", "first"): ("lz_a2c_param_count", "lz_ppo_workspace_bytes", "lz_ppo_grad_f32", False),
+    ("a2c", "hidden"): ("lz_a2c_param_count_hidden", "lz_a2c_workspace_bytes_hidden",
+                        "lz_a2c_grad_hidden_f32", True),
+    ("ppo", "hidden"): ("lz_a2c_param_count_hidden", "lz_ppo_workspace_bytes_hidden",
+                        "lz_ppo_grad_hidden_f32", True),
+    ("ppo", "wide"): ("lz_ppo_param_count_wide", "lz_ppo_workspace_bytes_wide", "lz_ppo_grad_wide_f32", True),
+}
+for (_kind, _), (_count, _ws, _grad, _h) in GRAD_ENTRIES.items():
+    _dims = [ctypes.c_int32] * (3 if _h else 2)  # obs_dim, act_dim[, hidden]
+    _SIGS[_count] = (ctypes.c_int64, _dims)
+    _SIGS[_ws] = (ctypes.c_int64, [ctypes.c_int64] + _dims + [ctypes.c_int32])
+    _SIGS[_grad] = (ctypes.c_int, [ctypes.POINTER(LzA2cGradArgs if _kind == "a2c" else LzPpoGradArgs),
+                                   ctypes.c_int32, VP])
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(

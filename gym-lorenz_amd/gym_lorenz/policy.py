@@ -1212,30 +1212,42 @@ def net_arch_hidden(net_arch, who="net_arch"):
 
 
 def _grad_fns(kind, hidden, O, A, who, wide=False):
-    """(P, workspace_bytes(n, max_workgroups), grad entry point) for a hidden size: the
-    first entry points at HIDDEN, the _hidden ones (lz_a2c_grad_hidden_f32, ...) otherwise;
-    wide (PPO only): the _wide ones, the 64-unit net on up to 24 inputs."""
+    """(P, workspace_bytes(n, max_workgroups), grad entry point) of _native.GRAD_ENTRIES' row
+    for a hidden size: the first entry points at HIDDEN, the _hidden ones
+    (lz_a2c_grad_hidden_f32, ...) otherwise; wide (PPO only): the _wide ones, the 64-unit net
+    on up to 24 inputs."""
     H = int(hidden)
-    if wide:
-        if kind != "ppo":
-            raise nat.LorenzEnvError(nat.LZ_ERR_UNSUPPORTED, "%s: the wide gradient is PPO's" % who)
-        P = int(nat.lib.lz_ppo_param_count_wide(O, A, H))
-        if P < 0:
-            raise nat.LorenzEnvError(nat.LZ_ERR_UNSUPPORTED, "%s: the wide gradient takes obs_dim "
-                                     "1..24, act_dim 1..4 and hidden 64" % who)
-        ws = nat.lib.lz_ppo_workspace_bytes_wide
-        return P, (lambda n, cap: int(ws(n, O, A, H, cap))), nat.lib.lz_ppo_grad_wide_f32
-    if nat.lib.lz_a2c_param_count(O, A) < 0:
+    if wide and kind != "ppo":
+        raise nat.LorenzEnvError(nat.LZ_ERR_UNSUPPORTED, "%s: the wide gradient is PPO's" % who)
+    if not wide and nat.lib.lz_a2c_param_count(O, A) < 0:
         raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "%s: obs_dim must be 1..8, act_dim 1..4" % who)
-    if H == HIDDEN:
-        P = int(nat.lib.lz_a2c_param_count(O, A))
-        ws = getattr(nat.lib, "lz_%s_workspace_bytes" % kind)
-        return P, (lambda n, cap: int(ws(n, O, A, cap))), getattr(nat.lib, "lz_%s_grad_f32" % kind)
-    P = int(nat.lib.lz_a2c_param_count_hidden(O, A, H))
+    row = nat.GRAD_ENTRIES[kind, "wide" if wide else "first" if H == HIDDEN else "hidden"]
+    count, ws, grad = (getattr(nat.lib, name) for name in row[:3])
+    h = (H,) if row[3] else ()
+    P = int(count(O, A, *h))
     if P < 0:
-        raise nat.LorenzEnvError(nat.LZ_ERR_UNSUPPORTED, "%s: hidden must be 64 or 128" % who)
-    ws = getattr(nat.lib, "lz_%s_workspace_bytes_hidden" % kind)
-    return P, (lambda n, cap: int(ws(n, O, A, H, cap))), getattr(nat.lib, "lz_%s_grad_hidden_f32" % kind)
+        raise nat.LorenzEnvError(nat.LZ_ERR_UNSUPPORTED, "%s: %s" % (
+            who, "the wide gradient takes obs_dim 1..24, act_dim 1..4 and hidden 64" if wide
+            else "hidden must be 64 or 128"))
+    return P, (lambda n, cap: int(ws(n, O, A, *h, cap))), grad
+
+
+def _launch_grad(who, fns, g, n, tail, max_workgroups, workspace, out, dev):
+    """The end of a2c_grad / ppo_grad: g's workspace and grad_sums [P + tail] (allocated when
+    None, checked either way) for n samples, then the launch on the current stream."""
+    P, ws_bytes, grad_fn = fns
+    need = ws_bytes(n, int(max_workgroups))
+    if need < 0:
+        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "%s: empty batch or bad max_workgroups" % who)
+    if workspace is None:
+        workspace = torch.empty((need // 8,), dtype=torch.float64, device=dev)
+    g.workspace = check_buffer(workspace, "workspace", torch.float64, need // 8, dev, at_least=True)
+    g.workspace_bytes = workspace.numel() * 8
+    if out is None:
+        out = torch.empty((P + tail,), dtype=torch.float64, device=dev)
+    g.grad_sums = check_buffer(out, "grad_sums", torch.float64, P + tail, dev)
+    nat.check(grad_fn(ctypes.byref(g), dev.index, _stream_ptr(dev)))
+    return out
 
 
 def a2c_grad(params, observations, actions, advantages, returns, obs_dim, act_dim, vf_coef=0.5,
@@ -1248,11 +1260,11 @@ def a2c_grad(params, observations, actions, advantages, returns, obs_dim, act_di
     O, A = int(obs_dim), int(act_dim)
     if dev.type != "cuda":
         raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "a2c_grad: params must be a device tensor")
-    P, ws_bytes, grad_fn = _grad_fns("a2c", hidden, O, A, "a2c_grad")
+    fns = _grad_fns("a2c", hidden, O, A, "a2c_grad")
     B = int(advantages.numel())
     f32 = torch.float32
     g = nat.LzA2cGradArgs()
-    g.params = check_buffer(params, "params", f32, P, dev)
+    g.params = check_buffer(params, "params", f32, fns[0], dev)
     g.observations = check_buffer(observations, "observations", f32, B * O, dev)
     g.actions = check_buffer(actions, "actions", f32, B * A, dev)
     g.advantages = check_buffer(advantages, "advantages", f32, B, dev)
@@ -1260,18 +1272,7 @@ def a2c_grad(params, observations, actions, advantages, returns, obs_dim, act_di
     g.n_samples, g.obs_dim, g.act_dim, g.hidden = B, O, A, int(hidden)
     g.max_workgroups = int(max_workgroups)
     g.vf_coef, g.ent_coef = float(vf_coef), float(ent_coef)
-    need = ws_bytes(B, int(max_workgroups))
-    if need < 0:
-        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "a2c_grad: empty batch or bad max_workgroups")
-    if workspace is None:
-        workspace = torch.empty((need // 8,), dtype=torch.float64, device=dev)
-    g.workspace = check_buffer(workspace, "workspace", torch.float64, need // 8, dev, at_least=True)
-    g.workspace_bytes = workspace.numel() * 8
-    if out is None:
-        out = torch.empty((P + 4,), dtype=torch.float64, device=dev)
-    g.grad_sums = check_buffer(out, "grad_sums", torch.float64, P + 4, dev)
-    nat.check(grad_fn(ctypes.byref(g), dev.index, _stream_ptr(dev)))
-    return out
+    return _launch_grad("a2c_grad", fns, g, B, 4, max_workgroups, workspace, out, dev)
 
 
 def a2c_apply(grad_sums, params, square_avg, lr, max_grad_norm=0.5, alpha=0.99, eps=1e-5,
@@ -1508,12 +1509,12 @@ def ppo_grad(params, observations, actions, advantages, returns, old_log_prob, o
     O, A = int(obs_dim), int(act_dim)
     if dev.type != "cuda":
         raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "ppo_grad: params must be a device tensor")
-    P, ws_bytes, grad_fn = _grad_fns("ppo", hidden, O, A, "ppo_grad", wide)
+    fns = _grad_fns("ppo", hidden, O, A, "ppo_grad", wide)
     n_rows = int(advantages.numel())
     cvf = 0.0 if clip_range_vf is None else float(clip_range_vf)
     f32 = torch.float32
     g = nat.LzPpoGradArgs()
-    g.params = check_buffer(params, "params", f32, P, dev)
+    g.params = check_buffer(params, "params", f32, fns[0], dev)
     g.observations = check_buffer(observations, "observations", f32, n_rows * O, dev)
     g.actions = check_buffer(actions, "actions", f32, n_rows * A, dev)
     g.advantages = check_buffer(advantages, "advantages", f32, n_rows, dev)
@@ -1527,18 +1528,7 @@ def ppo_grad(params, observations, actions, advantages, returns, old_log_prob, o
     g.clip_range, g.clip_range_vf = float(clip_range), cvf
     g.adv_moments = check_buffer(adv_moments, "adv_moments", torch.float64, 2, dev, required=False)
     g.ctrl = check_buffer(ctrl, "ctrl", torch.int64, 2, dev, required=False)
-    need = ws_bytes(M, int(max_workgroups))
-    if need < 0:
-        raise nat.LorenzEnvError(nat.LZ_ERR_INVALID, "ppo_grad: empty batch or bad max_workgroups")
-    if workspace is None:
-        workspace = torch.empty((need // 8,), dtype=torch.float64, device=dev)
-    g.workspace = check_buffer(workspace, "workspace", torch.float64, need // 8, dev, at_least=True)
-    g.workspace_bytes = workspace.numel() * 8
-    if out is None:
-        out = torch.empty((P + 6,), dtype=torch.float64, device=dev)
-    g.grad_sums = check_buffer(out, "grad_sums", torch.float64, P + 6, dev)
-    nat.check(grad_fn(ctypes.byref(g), dev.index, _stream_ptr(dev)))
-    return out
+    return _launch_grad("ppo_grad", fns, g, M, 6, max_workgroups, workspace, out, dev)
 
 
 def adam_apply(grad_sums, params, exp_avg, exp_avg_sq, ctrl, lr, max_grad_norm=0.5, betas=(0.9, 0.999),
